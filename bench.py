@@ -6,9 +6,14 @@
 
 A "step" is one `CycleVAEGAN.training_step` (generator update + discriminator update) on one
 synthetic batch per rank; batches are generated on the device before the timed region.  Rank 0
-prints ONE JSON line.  `roofline` is measured live with HIP events around every launch of the
-dominant DEVICE kernel during two extra instrumented steps (events recorded inside libvcg, vcg_profile_enable); `cpu_baseline` times the
-oracle's CPU restatement of the same step on a bounded sample (rank 0, N=1 only).
+prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps and prints the line
+(images/s, ms_per_step); `--dump-outputs DIR` first writes what the last timed step computed
+(dump_outputs).  Everything else runs only with `--full`: `roofline` is measured live with HIP
+events around every launch of the dominant DEVICE kernel during two extra instrumented steps (events
+recorded inside libvcg, vcg_profile_enable); `cpu_baseline` times the oracle's CPU restatement of the
+same step on a bounded sample and `rocm_eager_baseline` the same step through stock PyTorch-ROCm
+eager ops in a child process (rank 0, N=1 only).  --no-roofline / --no-cpu-baseline /
+--no-eager-baseline leave one of them out of a --full run.
 """
 import argparse
 import gc
@@ -69,7 +74,14 @@ def main():
     ap.add_argument("--eager-child", action="store_true", help=argparse.SUPPRESS)      # internal: the rocm_eager_baseline child process
     ap.add_argument("--no-eager-baseline", action="store_true",
                     help="skip the stock PyTorch-ROCm (MIOpen / rocBLAS eager) run of the same step beside cpu_baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure the roofline (two extra instrumented steps), the CPU baseline and "
+                         "the stock PyTorch-ROCm baseline (each unless its --no-* option is given)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.eager_child:
         # a process of its own (spawned by rocm_eager_baseline below): a MIOpen fault or hang there cannot take the bench line with it
@@ -263,6 +275,8 @@ def main():
         ex = torch.tensor([red.exposed_ms() / args.steps], dtype=torch.float64, device=dev)
         dist.all_reduce(ex, op=dist.ReduceOp.MAX)
         exposed_ms = ex.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, model)      # before anything else steps the model
     bad = [k for k, v in last.items() if v != v or abs(v) == float("inf")]
     if bad:
         raise SystemExit(f"non-finite metrics after the timed steps: {bad}")
@@ -297,15 +311,15 @@ def main():
                            "bucket_bytes": red.bucket_elems * 4, "is": "sum-all-reduce (RCCL) of contiguous slices of each optimizer's flat "
                            "gradient buffer, launched as their last weight gradient is issued; exchange_exposed_ms = time the compute stream "
                            "spent waiting for them before the optimizer steps, per step, max over ranks"}
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # every rank runs the two extra (untimed) steps: with N > 1 they contain the gradient exchange, which all
         # ranks must enter; rank 0 reports its own kernels
         roof = measure_roofline(pkg, model, pool, wl, B, S, latent, ms_per_step, rank)
         if rank == 0:
             out.update(roof)
-    if rank == 0 and not dist_on and not args.no_cpu_baseline and wl in ("cyclevaegan", "vae", "autoencoder"):
+    if args.full and rank == 0 and not dist_on and not args.no_cpu_baseline and wl in ("cyclevaegan", "vae", "autoencoder"):
         out["cpu_baseline"] = cpu_baseline(pkg, wl, S, latent)
-    if rank == 0 and not dist_on and not args.no_eager_baseline and wl in ("cyclevaegan", "vae", "autoencoder"):
+    if args.full and rank == 0 and not dist_on and not args.no_eager_baseline and wl in ("cyclevaegan", "vae", "autoencoder"):
         del model, pool
         gc.unfreeze()
         gc.collect()
@@ -317,6 +331,30 @@ def main():
         print(json.dumps(out), flush=True)
     if dist_on:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 48 << 20    # --dump-outputs writes at most this much (the headline model: 96 tensors, 10 MB)
+DUMP_SAMPLE = 1 << 16           # elements kept of a larger tensor
+
+
+def dump_outputs(path, last, model):
+    """What the last timed step computed, as path/<name>.npy: the metric dict training_step returned (metric.<key>.npy, float64
+    scalars) and every tensor of the state it updated — parameters, spectral-norm vectors — (param.<state_dict name>.npy,
+    float32, flattened).  A tensor larger than the per-tensor share of DUMP_BUDGET_BYTES is written as a fixed sample: indices
+    drawn without replacement by a generator seeded with the CRC-32 of its name, in ascending order, the same in every run."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for k, v in last.items():
+        np.save(os.path.join(path, f"metric.{k}.npy"), np.asarray(float(v), dtype=np.float64))
+    sd = model.state_dict()
+    keep = max(1, min(DUMP_SAMPLE, DUMP_BUDGET_BYTES // 4 // max(len(sd), 1)))
+    for name, t in sd.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > keep:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), keep, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, f"param.{name}.npy"), flat.to(torch.float32).cpu().numpy())
 
 
 PROFILE_ROUND = "r04"          # profiles/<round>_pmc_*.json: the committed PMC passes `traffic` and `mfma_pipe_util` are quoted from
@@ -481,7 +519,7 @@ def cpu_baseline(pkg, wl, S, latent):
     two timed ones — a bounded ~10-30 s sample of the workload (the full batch-8 step takes ~40 s on 8 cores)."""
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     oracle = importlib.import_module("vcg_oracle")
-    cores = min(os.cpu_count() or 1, 32)
+    cores = min(int(os.environ.get("OMP_NUM_THREADS") or 0) or os.cpu_count() or 1, 32)   # the CPUs this process may use, where set
     torch.set_num_threads(cores)
     Nn = pkg.Networks
     torch.manual_seed(1234)
