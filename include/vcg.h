@@ -280,6 +280,19 @@ int vcg_input_color_jitter(float* img, const float* jitter, int N, int S, void* 
 int vcg_input_prejitter(const unsigned char* arena, const int32_t* frames, const float* jitter, const int32_t* var,
                         float* fbuf, int N, void* stream);
 
+/* Evaluation (test.py) --------------------------------------------------------------------------------------------------- */
+/* Per-image quality of N outputs against N targets, both (N, S, S, 4) fp32 (the networks' layout, channels 0..2 used), the output
+   clamped to [0, 1], the target as given: result[n][4] = l1, mse, psnr (10 log10(1 / mse); +inf when mse == 0), ssim (11 x 11
+   Gaussian window, sigma 1.5, valid positions only, C1 = 0.01^2, C2 = 0.03^2, population moments, mean over positions and
+   channels).  New: the reference has no metric.  S >= 11.  ws: at least N * ceil(S / 16)^2 * 4 floats (16-byte aligned); each
+   tile's partial sums go to a slot of their own and are summed in a fixed order: the result of an image does not depend on the
+   batch it is in.  csrc/metrics.hip. */
+int vcg_image_metrics(const float* out, const float* target, float* result, int N, int S, float* ws, size_t ws_bytes,
+                      void* stream);
+/* (N, S, S, 4) fp32 -> contiguous (N, S, S, 3): fp32 clamp(0, 1), or (as_uint8) uint8 floor(255 v + 0.5) clipped to 0..255 — the
+   images test.py:317-343 builds on the host with clamp / permute / numpy (figures), and the PNGs of --save_images. */
+int vcg_to_display(const float* x, void* out, int N, int S, int as_uint8, void* stream);
+
 /* torch.optim.Adam.step — call sites Networks.py:312,894,1928-1935 ---------- */
 /* single-tensor torch formula on one flat buffer:
    m += (1-b1)(g-m); v = b2 v + (1-b2) g^2; p -= step_size * m / (sqrt(v)/bc2_sqrt + eps)

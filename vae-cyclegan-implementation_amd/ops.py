@@ -1252,3 +1252,41 @@ def adam_step_flat(p, g, m, v, step, lr, beta1, beta2, eps, grad_scale=1.0):
     _native.check(_native.lib().vcg_adam_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), step_size, beta1, beta2,
                                               1.0 - beta1, 1.0 - beta2, eps, bc2_sqrt, grad_scale, _stream()), "vcg_adam_step")
     PARAM_EPOCH[0] += 1
+
+
+# ------------------------------------------------------------------ evaluation (test.py)
+def _images_phys(t, what):
+    """A logical (N, 3, S, S) image batch -> its (N, S, S, 4) physical buffer (alias or converted copy)."""
+    if t.dim() != 4 or t.shape[1] != 3 or t.shape[2] != t.shape[3]:
+        raise RuntimeError(f"{what}: expected an (N, 3, S, S) image batch, got shape {tuple(t.shape)}")
+    return as_phys(t)
+
+
+def image_metrics(out, target):
+    """Per-image [l1, mse, psnr, ssim] of clamp(out, 0, 1) against `target`, both logical (N, 3, S, S) with S >= 11 ->
+    an (N, 4) fp32 device tensor (psnr is +inf where mse == 0).  csrc/metrics.hip has the definitions."""
+    _require_gpu(out, "image_metrics")
+    _require_gpu(target, "image_metrics")
+    if out.shape != target.shape:
+        raise RuntimeError(f"image_metrics: shape mismatch {tuple(out.shape)} vs {tuple(target.shape)}")
+    op, tp = _images_phys(out, "image_metrics"), _images_phys(target, "image_metrics")
+    n, s = out.shape[0], out.shape[2]
+    if s < 11:
+        raise RuntimeError(f"image_metrics: SSIM's 11x11 window needs images of at least 11x11, got {s}x{s}")
+    tiles = (s + 15) // 16
+    ws = torch.empty(n * tiles * tiles * 4, dtype=torch.float32, device=out.device)
+    res = torch.empty((n, 4), dtype=torch.float32, device=out.device)
+    _native.check(_native.lib().vcg_image_metrics(_ptr(op), _ptr(tp), _ptr(res), n, s, _ptr(ws), ws.numel() * 4, _stream()),
+                  "vcg_image_metrics")
+    return res
+
+
+def to_display(x, uint8=False):
+    """Logical (N, 3, S, S) images -> contiguous (N, S, S, 3) on the device: fp32 clamped to [0, 1], or uint8
+    floor(255 v + 0.5) clipped to 0..255 (PNG pixels)."""
+    _require_gpu(x, "to_display")
+    xp = _images_phys(x, "to_display")
+    n, s = x.shape[0], x.shape[2]
+    dst = torch.empty((n, s, s, 3), dtype=torch.uint8 if uint8 else torch.float32, device=x.device)
+    _native.check(_native.lib().vcg_to_display(_ptr(xp), _ptr(dst), n, s, 1 if uint8 else 0, _stream()), "vcg_to_display")
+    return dst

@@ -217,6 +217,14 @@ def build_parser():
     return p
 
 
+def split_indices(n, test_split, seed):
+    """(train, test) sample indices of a hypersim set of n samples: the reference's random_split (train.py:208-214) as a
+    permutation drawn from the run's --seed, so that test.py evaluates on exactly what a run held out."""
+    order = np.random.RandomState(seed).permutation(n)
+    ntrain = int((1 - test_split) * n) if test_split > 0 else n
+    return order[:ntrain], order[ntrain:]
+
+
 def create_dataloaders(args, device, rank, world, epoch_seed):
     """reference train.py:174-357 (create_dataloaders_hypersim / _maps / _summer2winter) on the device-side input pipeline:
     PIL decodes, the MI355X flips, crops, resamples, jitters and converts (input_pipeline.py), from the reference's directory
@@ -232,14 +240,14 @@ def create_dataloaders(args, device, rank, world, epoch_seed):
             raise ValueError("--dataset hypersim needs --source_modality (and --target_modality)")
         full = input_pipeline.HypersimFolders(os.path.join(args.data_dir, "hypersim"), mods, paired=args.paired or len(mods) == 1)
         kw = dict(num_workers=max(1, args.num_workers), same_xy=len(mods) == 1, rank=rank, world=world)
-        order = np.random.RandomState(args.seed).permutation(len(full))
-        ntrain = int((1 - args.test_split) * len(full)) if args.test_split > 0 else len(full)
+        train_idx, test_idx = split_indices(len(full), args.test_split, args.seed)
+        ntrain = len(train_idx)
         print(f"Training samples: {ntrain}" + (f", Testing samples: {len(full) - ntrain}" if args.test_split > 0 else ""))
-        train = input_pipeline.DeviceInputPipeline(full.subset(order[:ntrain]), args.batch_size, args.image_size, device,
+        train = input_pipeline.DeviceInputPipeline(full.subset(train_idx), args.batch_size, args.image_size, device,
                                                    recipe="hypersim", shuffle=True, seed=epoch_seed, **kw)
         test = None
-        if args.test_split > 0 and ntrain < len(full):
-            test = input_pipeline.DeviceInputPipeline(full.subset(order[ntrain:]), args.batch_size, args.image_size, device,
+        if len(test_idx):
+            test = input_pipeline.DeviceInputPipeline(full.subset(test_idx), args.batch_size, args.image_size, device,
                                                       recipe="hypersim", shuffle=False, seed=epoch_seed, **kw)
         return train, test
     root = os.path.join(args.data_dir, args.dataset)

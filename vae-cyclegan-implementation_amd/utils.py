@@ -87,6 +87,19 @@ def load_checkpoint(model, filename, device):
     return epoch, loss
 
 
+def load_model_weights(model, filename):
+    """test.py:110-143: the parameters of a checkpoint and nothing else, for inference.  Unlike `load_checkpoint` this configures
+    no optimizer, loads no Adam state (which would double the memory of every loaded model) and leaves the eps stream alone (the
+    evaluator seeds it itself).  Returns the checkpoint's other entries (epoch, loss, args)."""
+    if not os.path.exists(filename):
+        raise FileNotFoundError(f"No checkpoint found at {filename}")
+    checkpoint = torch.load(filename, map_location="cpu", weights_only=False)
+    model.load_state_dict(checkpoint.pop("model_state_dict"))
+    ops.PARAM_EPOCH[0] += 1                              # load_state_dict wrote through .data: drop every weight pack
+    checkpoint.pop("optimizer_states", None)
+    return checkpoint
+
+
 def _to_cpu(obj):
     if isinstance(obj, torch.Tensor):
         return obj.detach().cpu()
