@@ -148,3 +148,23 @@ def test_product_path_refuses_cpu_tensors(pkg):
         m(torch.zeros(1, 4, 4, 4))
     with pytest.raises(RuntimeError):
         pkg.optim.FusedAdam(m.parameters(), lr=1e-3)
+
+
+def test_instance_norm_cases_hit_every_ragged_plan(pkg):
+    """tests/test_gpu_norm_misc.py mirrors vcg_norm_plan (csrc/vcg_common.h) in Python: the mirror must agree with the plan the
+    library sizes its workspace by (ws = N nchunk C 20 + N C 8 + 512 bytes exposes nchunk), and the InstanceNorm case list must
+    keep hitting the ragged parts of the plan: the model's layers all split evenly, so a plan change could silently turn the edge
+    cases into easy ones."""
+    from test_gpu_norm_misc import IN_SHAPES, norm_plan, plan_edges
+    lib = pkg._native.lib()
+    for N, H, W, C in IN_SHAPES:
+        HW = H * W
+        ws = lib.vcg_in_workspace(N, HW, C)
+        assert (ws - 512 - N * C * 8) % (N * C * 20) == 0, (N, H, W, C, ws)
+        assert (ws - 512 - N * C * 8) // (N * C * 20) == norm_plan(N, HW, C)["nchunk"], (N, H, W, C)
+    hit = {}
+    for N, H, W, C in IN_SHAPES:
+        for k, v in plan_edges(N, H * W, C).items():
+            hit[k] = hit.get(k, False) or v
+    missing = [k for k, v in hit.items() if not v]
+    assert not missing, f"no InstanceNorm case runs: {missing}"
