@@ -160,7 +160,8 @@ int vcg_conv_pre_ok(const int32_t* cd);
 int vcg_conv_fwd_in_pre(const float* t_prev, const float* pre_mean, const float* pre_rstd, int pre_act, const float* wf,
                         const float* bias, float* y, float* mean, float* rstd, float eps, float* saved, const int32_t* cd,
                         void* ws, size_t ws_bytes, void* stream);
-/* dx = conv^T(dy) including the adjoint of the reflect padding.              */
+/* dx = conv^T(dy) including the adjoint of the reflect padding.  Every element of dx is written: the pad channels
+   dx[..., cin_log:] as exact zeros (tests/test_gpu_conv_plans.py checks it on every launch plan). */
 size_t vcg_conv_dgrad_workspace(const int32_t* cd);
 int vcg_conv_dgrad(const float* dy, const float* wf, float* dx, const int32_t* cd,
                    void* ws, size_t ws_bytes, void* stream);

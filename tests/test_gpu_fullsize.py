@@ -140,6 +140,30 @@ def test_conv_layer_at_headline_size(B, layer, pkg, device):
     err = ((bd.grad.double() - dbref).norm() / dbref.norm()).item()
     assert err <= DW_TOL, f"{name}: bias gradient differs from the float64 column sums by {err:.2e}"
 
+    # data gradient, element by element: the first and the last image against a float64 autograd convolution of those
+    # images, to the per-element bound of tests/test_gpu_conv_plans.py (c_path U |g| * |w| + the amax floor)
+    from test_gpu_conv_plans import FP16_DGRAD, U, _c_path, conv_plan
+    pd = conv_plan(spec.desc(B, h, h))["dgrad"]
+    kd = k * k * cout
+    wino = pd["branch"] == "wino"
+    c = _c_path(pd["branch"] in FP16_DGRAD or (pd["branch"] == "thin_fold" and bool(pd["kernel"])), kd, pd["nsplit"] + 9, wino)
+    floor = 2.0 ** -40 * 2 * 4 * kd * g.abs().max().item() * w.abs().max().item() * (16 if wino else 1)
+
+    def conv64(xi, wi):
+        xl = F.pixel_unshuffle(xi, 2) if ups == 2 else xi
+        return F.conv2d(F.pad(xl, (pad, pad, pad, pad), mode="reflect"), wi, stride=stride)
+
+    for i in (0, B - 1):
+        xi = x[i:i + 1].double().requires_grad_(True)
+        ref, = torch.autograd.grad(conv64(xi, w.double()), xi, g[i:i + 1].double())
+        xa = xi.detach().abs().requires_grad_(True)
+        mag, = torch.autograd.grad(conv64(xa, w.double().abs()), xa, g[i:i + 1].double().abs())
+        r = (dx[i:i + 1].double() - ref).abs() / (c * U * mag + floor)
+        worst = r.max().item()
+        assert worst <= 1.0, (f"{name}: data gradient of image {i}: element {int(r.argmax())} off by {worst:.3g} x its bound "
+                              f"({pd['branch']}, c_path {c:.1f})")
+        del xi, ref, xa, mag, r
+
 
 # layers whose output goes into an InstanceNorm (Networks.py:93-95, 110-115, 128-130, 244-247): epilogue activation as in the model
 # (ReLU before the norm in D / U / R.conv1, none in CaSb — the stem and the discriminators' normalised layers)

@@ -168,3 +168,49 @@ def test_instance_norm_cases_hit_every_ragged_plan(pkg):
             hit[k] = hit.get(k, False) or v
     missing = [k for k, v in hit.items() if not v]
     assert not missing, f"no InstanceNorm case runs: {missing}"
+
+
+def _plan_sweep():
+    """a few hundred geometries across the plans' conditions: channels 4..2048, k 1/3/4/7, stride 1/2, ups 1/2, reflect / zero,
+    maps 2..256, N 1..16, logical channels below the pitch"""
+    import random
+    from test_gpu_conv_plans import desc
+    rng = random.Random(20261016)
+    out = []
+    while len(out) < 400:
+        k = rng.choice([1, 3, 4, 7])
+        s = rng.choice([1, 2])
+        ups = rng.choice([1, 2]) if s == 1 else 1
+        cin = rng.choice([4, 8, 16, 32, 64, 128, 192, 256, 512, 1024, 2048])
+        cout = rng.choice([4, 8, 32, 64, 128, 192, 256, 512, 1024, 2048])
+        hl = rng.choice([2, 3, 4, 5, 6, 7, 8, 12, 16, 17, 20, 32, 64, 66, 128, 256])
+        wl = hl if rng.random() < 0.8 else rng.choice([3, 6, 9, 16, 64])
+        pad = {1: 0, 3: 1, 4: 1, 7: 3}[k]
+        refl = rng.choice([0, 1])
+        if refl and (pad >= hl or pad >= wl) or hl + 2 * pad < k or wl + 2 * pad < k:
+            continue
+        cin_log = cin if rng.random() < 0.7 else cin - rng.choice([1, 2, 3])
+        cout_log = cout if rng.random() < 0.7 else cout - 1
+        out.append(desc(rng.choice([1, 2, 3, 4, 8, 16]), hl * ups, wl * ups, cin, cout, k, s, pad, refl, ups, rng.choice(range(5)),
+                        cin_log, cout_log))
+    return out
+
+
+def test_conv_plan_mirror_matches_the_library_and_cases_hit_every_branch(pkg):
+    """tests/test_gpu_conv_plans.py mirrors the convolution dispatch (conv_plan).  Without a GPU the library reports the sizes its
+    planners derive — forward / data / weight gradient workspaces, packed-weight floats, whether Wf is read, saved floats, whether
+    the normalising gather exists — which encode the K-slice, Winograd, slab, ring, thin and swapped choices: the mirror must
+    give the same numbers for the GPU case list and a sweep of 400 geometries.  And the case list must keep reaching every branch
+    of the module's table: a plan change that turns an edge case into an easy one fails here, naming the branch."""
+    from test_gpu_conv_plans import CASES, REQUIRED, branch_labels, case_desc, library_sizes, mirror_sizes
+    lib = pkg._native.lib()
+    cds = [case_desc(c) for c in CASES] + _plan_sweep()
+    for cd in cds:
+        assert lib.vcg_pack_weight_floats(cd) > 0, (list(cd), lib.vcg_last_error())
+        got, want = library_sizes(lib, cd), mirror_sizes(cd)
+        assert got == want, f"descriptor {list(cd)[:14]}: library {got} mirror {want}"
+    hit = set()
+    for c in CASES:
+        hit |= branch_labels(case_desc(c), c[2])
+    missing = [r for r in REQUIRED if r not in hit]
+    assert not missing, f"no convolution case reaches: {missing}"
