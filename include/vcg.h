@@ -294,6 +294,29 @@ int vcg_image_metrics(const float* out, const float* target, float* result, int 
    images test.py:317-343 builds on the host with clamp / permute / numpy (figures), and the PNGs of --save_images. */
 int vcg_to_display(const float* x, void* out, int N, int S, int as_uint8, void* stream);
 
+/* Whole images of any size (translate.py) --------------------------------------------------------------------------------- */
+/* N decoded frames of one size, uint8 (N, H, W, C) with C = 1 (grey, replicated), 3 or 4 (alpha dropped) -> (N, Hp, Wp, 4) fp32 in
+   the networks' layout, channel 3 = 0: Pillow's decoded array -> torchvision ToTensor -> numpy.pad(mode="reflect") -> the
+   pitch-4 copy, which the caller would otherwise make on the host.  Value: (float)v / 255.0f, a correctly rounded DIVISION as
+   ToTensor's, not v * (1.0f / 255) (which differs in the last bit for 126 byte values).  The frame sits at (top, left) of the
+   buffer; the border around it is filled by reflection WITHOUT repeating the edge pixel (row top - k holds source row k), so
+   each of the four borders must be narrower than the frame (top < H, Hp - H - top < H, likewise in x).  translate.py rounds
+   Hp, Wp up to multiples of 16 and centres the frame (top = (Hp - H) / 2).  src 4-byte aligned, out 16-byte aligned.
+   csrc/image_io.hip. */
+int vcg_image_load(const unsigned char* src, float* out, int N, int H, int W, int C, int Hp, int Wp, int top, int left,
+                   void* stream);
+/* vcg_to_display for the window (top, left, H, W) of an (N, Hp, Wp, 4) buffer -> contiguous (N, H, W, 3): the crop that undoes
+   vcg_image_load's padding and the display conversion in one pass, with vcg_to_display's rounding (for Hp = Wp = H = W and
+   top = left = 0 the same bytes). */
+int vcg_to_display_hw(const float* x, void* out, int N, int Hp, int Wp, int top, int left, int H, int W, int as_uint8,
+                      void* stream);
+/* vcg_image_metrics for the windows (top, left, H, W) of two (N, Hp, Wp, 4) buffers, H, W >= 11: the same definitions over the
+   H x W window (SSIM's valid positions are the (H - 10)(W - 10) of the window; nothing outside it is read), the same kernel,
+   the same tile slots summed in the same fixed order: for H = W = Hp = Wp = S it returns vcg_image_metrics's bits.
+   ws: at least N * ceil(H / 16) * ceil(W / 16) * 4 floats.  csrc/metrics.hip. */
+int vcg_image_metrics_hw(const float* out, const float* target, float* result, int N, int Hp, int Wp, int top, int left,
+                         int H, int W, float* ws, size_t ws_bytes, void* stream);
+
 /* torch.optim.Adam.step — call sites Networks.py:312,894,1928-1935 ---------- */
 /* single-tensor torch formula on one flat buffer:
    m += (1-b1)(g-m); v = b2 v + (1-b2) g^2; p -= step_size * m / (sqrt(v)/bc2_sqrt + eps)

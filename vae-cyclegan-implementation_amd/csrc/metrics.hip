@@ -29,11 +29,12 @@
 #define MT_THREADS (MT_TILE * MT_TILE)
 
 struct MetricsP {
-  const float4* out;     // (N, S, S, 4) fp32, channel 3 unused
+  const float4* out;     // (N, Hp, Wp, 4) fp32, channel 3 unused; the images are the windows (top, left, H, W) of the buffers
   const float4* tgt;
   float* ws;             // [N][tiles][4] partial sums: l1, squared error, ssim (channel-averaged), 0
   float* res;            // [N][4]: l1, mse, psnr, ssim
-  int S, tiles_x;        // tiles per image = tiles_x^2
+  int H, W, Hp, Wp, top, left;
+  int tiles_x, tiles_y;  // tiles per image = tiles_x * tiles_y, counted from the window's corner
   float w[MT_WIN];       // the Gaussian window, normalised in double on the host
 };
 
@@ -43,16 +44,16 @@ __global__ __launch_bounds__(MT_THREADS) void k_image_metrics(MetricsP p) {
   __shared__ float so[3][MT_STAGE * MT_STAGE], st[3][MT_STAGE * MT_STAGE];   // shifted pixels, by channel
   __shared__ float vm[15][MT_TILE * MT_STAGE];                                // vertical pass: [moment * 3 + channel][row][col]
   __shared__ float red[3][MT_THREADS];
-  const int S = p.S, tid = threadIdx.x;
+  const int H = p.H, W = p.W, S = p.Wp, tid = threadIdx.x;            // S: the row pitch in pixels
   const int n = blockIdx.z, y0 = blockIdx.y * MT_TILE, x0 = blockIdx.x * MT_TILE;
-  const size_t img = (size_t)n * S * S;
+  const size_t img = ((size_t)n * p.Hp + p.top) * p.Wp + p.left;    // the window's first pixel: nothing outside it is read
   const float4 ko4 = p.out[img + (size_t)y0 * S + x0], kt4 = p.tgt[img + (size_t)y0 * S + x0];
   const float ko[3] = {clamp01(ko4.x), clamp01(ko4.y), clamp01(ko4.z)}, kt[3] = {kt4.x, kt4.y, kt4.z};
 
   for (int i = tid; i < MT_STAGE * MT_STAGE; i += MT_THREADS) {
     const int r = i / MT_STAGE, c = i - r * MT_STAGE, y = y0 + r, x = x0 + c;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f), t = o;
-    bool in = y < S && x < S;              // outside the image: only windows that are not valid read these
+    bool in = y < H && x < W;              // outside the image: only windows that are not valid read these
     if (in) {
       o = p.out[img + (size_t)y * S + x];
       t = p.tgt[img + (size_t)y * S + x];
@@ -84,7 +85,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_image_metrics(MetricsP p) {
   // horizontal pass + SSIM at this thread's window position; L1 / squared error of its own pixel
   const int r = tid / MT_TILE, c = tid - r * MT_TILE, y = y0 + r, x = x0 + c;
   float ssim = 0.f, l1 = 0.f, se = 0.f;
-  if (y < S - (MT_WIN - 1) && x < S - (MT_WIN - 1)) {
+  if (y < H - (MT_WIN - 1) && x < W - (MT_WIN - 1)) {
     const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
     for (int ch = 0; ch < 3; ++ch) {
       float m[5];
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_image_metrics(MetricsP p) {
     }
     ssim *= (1.f / 3.f);
   }
-  if (y < S && x < S) {
+  if (y < H && x < W) {
     const float4 o = p.out[img + (size_t)y * S + x], t = p.tgt[img + (size_t)y * S + x];
     const float d0 = clamp01(o.x) - t.x, d1 = clamp01(o.y) - t.y, d2 = clamp01(o.z) - t.z;
     l1 = fabsf(d0) + fabsf(d1) + fabsf(d2);
@@ -119,14 +120,14 @@ __global__ __launch_bounds__(MT_THREADS) void k_image_metrics(MetricsP p) {
     __syncthreads();
   }
   if (tid == 0) {
-    float* slot = p.ws + ((size_t)n * p.tiles_x * p.tiles_x + (size_t)blockIdx.y * p.tiles_x + blockIdx.x) * 4;
+    float* slot = p.ws + ((size_t)n * p.tiles_x * p.tiles_y + (size_t)blockIdx.y * p.tiles_x + blockIdx.x) * 4;
     slot[0] = red[0][0]; slot[1] = red[1][0]; slot[2] = red[2][0]; slot[3] = 0.f;
   }
 }
 
 __global__ __launch_bounds__(256) void k_metrics_final(MetricsP p) {
   __shared__ float red[3][256];
-  const int n = blockIdx.x, tid = threadIdx.x, tiles = p.tiles_x * p.tiles_x;
+  const int n = blockIdx.x, tid = threadIdx.x, tiles = p.tiles_x * p.tiles_y;
   const float* ws = p.ws + (size_t)n * tiles * 4;
   float a = 0.f, b = 0.f, c = 0.f;
   for (int i = tid; i < tiles; i += 256) {          // each thread a fixed strided subset, in order
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(256) void k_metrics_final(MetricsP p) {
     __syncthreads();
   }
   if (tid == 0) {
-    const float npx = 3.f * (float)p.S * (float)p.S, nwin = (float)(p.S - (MT_WIN - 1)) * (float)(p.S - (MT_WIN - 1));
+    const float npx = 3.f * (float)p.H * (float)p.W, nwin = (float)(p.H - (MT_WIN - 1)) * (float)(p.W - (MT_WIN - 1));
     const float mse = red[1][0] / npx;
     float* o = p.res + (size_t)n * 4;
     o[0] = red[0][0] / npx;
@@ -153,15 +154,16 @@ __global__ __launch_bounds__(256) void k_metrics_final(MetricsP p) {
   }
 }
 
-extern "C" int vcg_image_metrics(const float* out, const float* target, float* result, int N, int S, float* ws, size_t ws_bytes,
-                                 void* stream) {
-  VCG_CHECK_ARG(out && target && result && ws, "vcg_image_metrics: null pointer");
-  VCG_CHECK_ARG(N > 0 && S >= MT_WIN && S <= 4096, "vcg_image_metrics: bad N=%d S=%d (SSIM's 11x11 window needs S >= 11)", N, S);
+// both entry points: the window (top, left, H, W) of two (N, Hp, Wp, 4) buffers
+static int metrics_launch(const char* who, const float* out, const float* target, float* result, int N, int Hp, int Wp, int top,
+                          int left, int H, int W, float* ws, size_t ws_bytes, void* stream) {
   MetricsP p;
-  p.out = (const float4*)out; p.tgt = (const float4*)target; p.ws = ws; p.res = result; p.S = S;
-  p.tiles_x = (S + MT_TILE - 1) / MT_TILE;
-  const size_t need = (size_t)N * p.tiles_x * p.tiles_x * 4 * sizeof(float);
-  VCG_CHECK_ARG(ws_bytes >= need, "vcg_image_metrics: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  p.out = (const float4*)out; p.tgt = (const float4*)target; p.ws = ws; p.res = result;
+  p.H = H; p.W = W; p.Hp = Hp; p.Wp = Wp; p.top = top; p.left = left;
+  p.tiles_x = (W + MT_TILE - 1) / MT_TILE;
+  p.tiles_y = (H + MT_TILE - 1) / MT_TILE;
+  const size_t need = (size_t)N * p.tiles_x * p.tiles_y * 4 * sizeof(float);
+  VCG_CHECK_ARG(ws_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
   double g[MT_WIN], sum = 0.0;
   for (int k = 0; k < MT_WIN; ++k) {
     const double d = k - (MT_WIN - 1) / 2;
@@ -169,10 +171,27 @@ extern "C" int vcg_image_metrics(const float* out, const float* target, float* r
     sum += g[k];
   }
   for (int k = 0; k < MT_WIN; ++k) p.w[k] = (float)(g[k] / sum);
-  hipLaunchKernelGGL(k_image_metrics, dim3(p.tiles_x, p.tiles_x, N), dim3(MT_THREADS), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(k_image_metrics, dim3(p.tiles_x, p.tiles_y, N), dim3(MT_THREADS), 0, (hipStream_t)stream, p);
   hipLaunchKernelGGL(k_metrics_final, dim3(N), dim3(256), 0, (hipStream_t)stream, p);
-  VCG_LAUNCH_CHECK("vcg_image_metrics");
+  VCG_LAUNCH_CHECK(who);
   return 0;
+}
+
+extern "C" int vcg_image_metrics(const float* out, const float* target, float* result, int N, int S, float* ws, size_t ws_bytes,
+                                 void* stream) {
+  VCG_CHECK_ARG(out && target && result && ws, "vcg_image_metrics: null pointer");
+  VCG_CHECK_ARG(N > 0 && S >= MT_WIN && S <= 4096, "vcg_image_metrics: bad N=%d S=%d (SSIM's 11x11 window needs S >= 11)", N, S);
+  return metrics_launch("vcg_image_metrics", out, target, result, N, S, S, 0, 0, S, S, ws, ws_bytes, stream);
+}
+
+extern "C" int vcg_image_metrics_hw(const float* out, const float* target, float* result, int N, int Hp, int Wp, int top, int left,
+                                    int H, int W, float* ws, size_t ws_bytes, void* stream) {
+  VCG_CHECK_ARG(out && target && result && ws, "vcg_image_metrics_hw: null pointer");
+  VCG_CHECK_ARG(N > 0 && N <= 65535 && H >= MT_WIN && W >= MT_WIN && Hp <= 65535 && Wp <= 65535,
+                "vcg_image_metrics_hw: bad N=%d H=%d W=%d (SSIM's 11x11 window needs H, W >= 11)", N, H, W);
+  VCG_CHECK_ARG(top >= 0 && left >= 0 && top + H <= Hp && left + W <= Wp,
+                "vcg_image_metrics_hw: the %dx%d window at (%d, %d) leaves the %dx%d buffer", H, W, top, left, Hp, Wp);
+  return metrics_launch("vcg_image_metrics_hw", out, target, result, N, Hp, Wp, top, left, H, W, ws, ws_bytes, stream);
 }
 
 // pitch-4 fp32 (N, S, S, 4) -> contiguous (N, S, S, 3): fp32 clamped to [0, 1], or uint8 floor(255 v + 0.5) clipped to 0..255

@@ -1290,3 +1290,94 @@ def to_display(x, uint8=False):
     dst = torch.empty((n, s, s, 3), dtype=torch.uint8 if uint8 else torch.float32, device=x.device)
     _native.check(_native.lib().vcg_to_display(_ptr(xp), _ptr(dst), n, s, 1 if uint8 else 0, _stream()), "vcg_to_display")
     return dst
+
+
+# ------------------------------------------------------------------ whole images of any size (translate.py)
+# The largest N * Hp * Wp (padded pixels of one batch) a generator forward accepts.  Every kernel a forward dispatches to computes
+# element offsets in size_t except the gathers of the direct convolution kernels (conv_igemm.hip, conv_slab.hip), which address
+# their input with 32-bit BYTE offsets and keep 0x80000000 as the "outside" mark; vcg_conv_fwd* therefore refuse an input of
+# 2 GiB or more.  The largest input of a generator is a 64-channel full-resolution map (the first D block's and the head's):
+# N * Hp * Wp * 64 * 4 bytes < 2^31.  DESIGN.md, "The translator".
+MAX_TRANSLATE_PIXELS = (1 << 31) // (64 * 4) - 1
+MIN_TRANSLATE_SIDE = 32           # the 1/16-resolution bottleneck is reflect-padded by 1: it must be at least 2 x 2
+
+
+def pad_plan(h, w):
+    """(Hp, Wp, top, left): H and W rounded up to multiples of 16 (four PixelUnshuffles), the frame centred in the padded one."""
+    hp, wp = (h + 15) // 16 * 16, (w + 15) // 16 * 16
+    return hp, wp, (hp - h) // 2, (wp - w) // 2
+
+
+def reflect_index(n, before, total):
+    """Source index of each of `total` padded positions of an axis of n samples that starts `before` positions early:
+    reflection without repeating the edge sample (numpy.pad(mode="reflect"), the convolutions' own padding)."""
+    i = [abs(k - before) for k in range(total)]
+    return [2 * (n - 1) - k if k >= n else k for k in i]
+
+
+def check_translate_size(n, h, w):
+    """Raise before anything is launched if a batch of n frames of h x w cannot go through a generator in one piece."""
+    if h < MIN_TRANSLATE_SIDE or w < MIN_TRANSLATE_SIDE:
+        raise RuntimeError(f"a {h}x{w} frame is smaller than {MIN_TRANSLATE_SIDE} on a side: after four halvings the bottleneck map "
+                           f"would be too small for its reflection padding")
+    hp, wp, _, _ = pad_plan(h, w)
+    if n * hp * wp > MAX_TRANSLATE_PIXELS:
+        raise RuntimeError(f"{n} frame(s) of {h}x{w} ({n * hp * wp} padded pixels) exceed ops.MAX_TRANSLATE_PIXELS = "
+                           f"{MAX_TRANSLATE_PIXELS}: the convolution kernels address a tensor with 32-bit byte offsets.  There is no "
+                           f"tiled fallback: InstanceNorm statistics are taken over the whole image, so tiles would not reproduce "
+                           f"the whole-frame result.  Use a smaller batch or a smaller frame")
+    return hp, wp
+
+
+def image_load(frames):
+    """uint8 device frames (N, H, W, C), C in (1, 3, 4) -> (logical (N, 3, Hp, Wp) nhwc batch in [0, 1], (top, left, H, W)): v / 255,
+    grey replicated, alpha dropped, padded by reflection to multiples of 16 with the frame centred (csrc/image_io.hip)."""
+    if not frames.is_cuda:
+        raise RuntimeError(f"image_load: expected a tensor on the MI355X (cuda) device, got {frames.device}; this package has no CPU path")
+    if frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[3] not in (1, 3, 4):
+        raise RuntimeError(f"image_load: expected uint8 (N, H, W, C) frames with C in (1, 3, 4), got {frames.dtype} {tuple(frames.shape)}")
+    src = frames.contiguous()
+    n, h, w, c = src.shape
+    hp, wp, top, left = pad_plan(h, w)
+    dst = torch.empty((n, hp, wp, 4), dtype=torch.float32, device=src.device)
+    _native.check(_native.lib().vcg_image_load(_ptr(src), _ptr(dst), n, h, w, c, hp, wp, top, left, _stream()), "vcg_image_load")
+    return logical_of(dst, 3), (top, left, h, w)
+
+
+def _window_of(t, window, what):
+    if t.dim() != 4 or t.shape[1] != 3:
+        raise RuntimeError(f"{what}: expected an (N, 3, H, W) image batch, got shape {tuple(t.shape)}")
+    n, _, hp, wp = t.shape
+    top, left, h, w = (0, 0, hp, wp) if window is None else window
+    if top < 0 or left < 0 or h < 1 or w < 1 or top + h > hp or left + w > wp:
+        raise RuntimeError(f"{what}: the window {tuple(window)} leaves the {hp}x{wp} images")
+    return n, hp, wp, top, left, h, w
+
+
+def to_display_hw(x, window=None, uint8=False):
+    """`to_display` for images of any height and width, cropped to `window` = (top, left, H, W) (None: the whole image)."""
+    _require_gpu(x, "to_display_hw")
+    n, hp, wp, top, left, h, w = _window_of(x, window, "to_display_hw")
+    xp = as_phys(x)
+    dst = torch.empty((n, h, w, 3), dtype=torch.uint8 if uint8 else torch.float32, device=x.device)
+    _native.check(_native.lib().vcg_to_display_hw(_ptr(xp), _ptr(dst), n, hp, wp, top, left, h, w, 1 if uint8 else 0, _stream()),
+                  "vcg_to_display_hw")
+    return dst
+
+
+def image_metrics_hw(out, target, window=None):
+    """`image_metrics` over `window` = (top, left, H, W) of two (N, 3, Hp, Wp) batches, H, W >= 11 (None: the whole images).
+    Nothing outside the window is read; for whole square images the result is `image_metrics`'s, bit for bit."""
+    _require_gpu(out, "image_metrics_hw")
+    _require_gpu(target, "image_metrics_hw")
+    if out.shape != target.shape:
+        raise RuntimeError(f"image_metrics_hw: shape mismatch {tuple(out.shape)} vs {tuple(target.shape)}")
+    n, hp, wp, top, left, h, w = _window_of(out, window, "image_metrics_hw")
+    if h < 11 or w < 11:
+        raise RuntimeError(f"image_metrics_hw: SSIM's 11x11 window needs images of at least 11x11, got {h}x{w}")
+    op, tp = as_phys(out), as_phys(target)
+    ws = torch.empty(n * ((h + 15) // 16) * ((w + 15) // 16) * 4, dtype=torch.float32, device=out.device)
+    res = torch.empty((n, 4), dtype=torch.float32, device=out.device)
+    _native.check(_native.lib().vcg_image_metrics_hw(_ptr(op), _ptr(tp), _ptr(res), n, hp, wp, top, left, h, w, _ptr(ws),
+                                                     ws.numel() * 4, _stream()), "vcg_image_metrics_hw")
+    return res

@@ -1,0 +1,389 @@
+#!/usr/bin/env python3
+"""Apply a trained generator to whole images of any size: `python translate.py --checkpoint RUN_OR_PTH --input FILE_OR_DIR
+--output DIR`.  New: the reference has no inference entry point (its test.py only walks runs/ and squeezes every sample to
+--image_size squared).
+
+The generators are fully convolutional, so a frame goes through in one piece: decoded with Pillow on host threads into a pinned
+buffer, copied to the device as uint8, converted and reflect-padded to multiples of 16 there (csrc/image_io.hip), run through
+the generator alone in eval mode, cropped and converted to uint8 on the device; only those bytes come back.  Frames of equal
+size are batched.  No tiling: InstanceNorm statistics are taken over the whole image, so tiles would not reproduce the
+whole-frame result; a batch above `ops.MAX_TRANSLATE_PIXELS` padded pixels is refused instead ("The translator").
+
+Directions: `a2b` is G (the one generator of autoencoder / vae / aegan / vaegan), `b2a` is F of the cycle models.  For doubleae /
+doublevae the two directions are the models' `translate_A_to_B` (decoder_B) and `translate_B_to_A` (decoder_A) — NOT what
+test.py shows for them, which is the reconstruction decoder_A(encoder(x)) their forward returns first.
+"""
+import argparse
+import json
+import math
+import os
+import sys
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+
+import numpy as np
+import torch
+
+if __package__ in (None, ""):
+    import importlib
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    _pkg = importlib.import_module("vae-cyclegan-implementation_amd")
+    ops, utils, input_pipeline = _pkg.ops, _pkg.utils, _pkg.input_pipeline
+    train = importlib.import_module("vae-cyclegan-implementation_amd.train")
+else:
+    from . import input_pipeline, ops, train, utils
+
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
+METRIC_NAMES = ("l1", "mse", "psnr", "ssim")
+ONE_GENERATOR = ("autoencoder", "vae", "aegan", "vaegan")
+VARIATIONAL = ("vae", "vaegan", "cyclevae", "cyclevaegan", "doublevae")
+
+
+# ------------------------------------------------------------------ the model
+def load_generator(checkpoint_or_run_dir, architecture=None, latent_dim=None, paired=None, device="cuda"):
+    """(model in eval mode, architecture) from a run directory (its args.json + best_model.pth, as test.load_model) or from a
+    bare .pth plus the arguments args.json would have given.  Parameters only: no optimizer state is loaded."""
+    path = Path(checkpoint_or_run_dir)
+    if path.is_dir():
+        with open(path / "args.json") as f:
+            a = json.load(f)
+        architecture = architecture or a["architecture"]
+        latent_dim = a.get("latent_dim", 64) if latent_dim is None else latent_dim
+        paired = a.get("paired", True) if paired is None else paired
+        path = path / "best_model.pth"
+    if architecture is None:
+        raise ValueError("a bare checkpoint file needs --architecture (a run directory has it in args.json)")
+    architecture = train.ALIASES.get(architecture, architecture)
+    model = train.create_model(architecture, paired=True if paired is None else paired,
+                               latent_dim=64 if latent_dim is None else latent_dim).to(device)
+    utils.load_model_weights(model, str(path))
+    model.eval()
+    return model, architecture
+
+
+def generator_of(model, architecture, direction="a2b"):
+    """The function logical nhwc batch -> translated batch of one direction of a model (see the module docstring)."""
+    arch = train.ALIASES.get(architecture, architecture)
+    if direction not in ("a2b", "b2a"):
+        raise ValueError(f"direction must be 'a2b' or 'b2a', got {direction!r}")
+    if arch not in train.REFERENCE_ARCHS:
+        raise ValueError(f"Unknown architecture: {architecture}")
+    if direction == "b2a" and arch in ONE_GENERATOR:
+        raise ValueError(f"{arch} has one generator (A -> B): there is no b2a direction to run")
+    if arch == "autoencoder":
+        return model
+    if arch == "vae":
+        return lambda x: model(x)[0]
+    if arch in ("doubleae", "doublevae"):
+        return model.translate_A_to_B if direction == "a2b" else model.translate_B_to_A
+    gen = model.G if direction == "a2b" else model.F
+    return (lambda x: gen(x)[0]) if arch in VARIATIONAL else gen
+
+
+def _latent_dim(model):
+    for m in model.modules():
+        if hasattr(m, "latent_dim") and hasattr(m, "muConv"):
+            return m.latent_dim
+    raise RuntimeError("eps='mean' on a variational architecture whose model has no variational block")
+
+
+def run_generator(model, architecture, x, direction="a2b", eps="sample", seed=1234):
+    """One direction of `model` on a logical (N, 3, Hp, Wp) batch (Hp, Wp multiples of 16), in eval mode without autograd.
+    eps: "sample" draws the reparameterisation noise from the ops stream (seeded with `seed` first unless it is None: the stream
+    goes on where it is); "mean" injects zeros, so a variational generator decodes mu and the output is deterministic."""
+    if eps not in ("sample", "mean"):
+        raise ValueError(f"eps must be 'sample' or 'mean', got {eps!r}")
+    arch = train.ALIASES.get(architecture, architecture)
+    gen = generator_of(model, arch, direction)
+    n, _, hp, wp = x.shape
+    if hp % 16 or wp % 16:
+        raise RuntimeError(f"run_generator: {hp}x{wp} is not a multiple of 16 on both sides (ops.image_load pads)")
+    ops.check_translate_size(n, hp, wp)
+    model.eval()
+    try:
+        if arch in VARIATIONAL:
+            if eps == "mean":
+                ops.inject_eps([torch.zeros((n, _latent_dim(model), hp // 16, wp // 16), dtype=torch.float32, device=x.device)])
+            elif seed is not None:
+                ops.manual_seed(seed)
+        with torch.no_grad():
+            return gen(ops.to_nhwc(x))
+    finally:
+        ops.inject_eps([])
+
+
+def _as_frames(frames):
+    """uint8 (N, H, W, C) tensor (wherever it lives) of an array, a tensor or a list of same-sized ones; grey (H, W) gets C = 1."""
+    if isinstance(frames, (list, tuple)):
+        items = [torch.from_numpy(np.array(f)) if not isinstance(f, torch.Tensor) else f for f in frames]      # a copy: Pillow's arrays are read-only
+        items = [f.unsqueeze(-1) if f.dim() == 2 else f for f in items]
+        if len({tuple(f.shape) for f in items}) != 1:
+            raise ValueError(f"frames of one call must have one size, got {sorted({tuple(f.shape) for f in items})}")
+        frames = torch.stack(items)
+    elif not isinstance(frames, torch.Tensor):
+        frames = torch.as_tensor(np.asarray(frames))
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0) if frames.shape[-1] in (1, 3, 4) else frames.unsqueeze(-1)
+    if frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[3] not in (1, 3, 4):
+        raise ValueError(f"expected uint8 frames (N, H, W, C) with C in (1, 3, 4), got {frames.dtype} {tuple(frames.shape)}")
+    return frames
+
+
+def translate_padded(model, architecture, frames, direction="a2b", eps="sample", seed=1234, device=None):
+    """(generator output as a logical (N, 3, Hp, Wp) batch, window (top, left, H, W) of the frames inside it)."""
+    frames = _as_frames(frames)
+    n, h, w, _ = frames.shape
+    generator_of(model, architecture, direction)                    # a wrong direction fails before anything is copied
+    ops.check_translate_size(n, h, w)                               # ... and so does a frame that cannot go through
+    device = device or next(model.parameters()).device
+    x, window = ops.image_load(frames.to(device, non_blocking=True))
+    return run_generator(model, architecture, x, direction, eps, seed), window
+
+
+def translate_images(model, architecture, frames, direction="a2b", eps="sample", seed=1234, return_float=False, device=None):
+    """uint8 frames (N, H, W, C) (array, tensor or list of same-sized ones; C = 1, 3 or 4) -> the translated frames on the device,
+    uint8 (N, H, W, 3) (`return_float`: fp32 clamped to [0, 1]).  Pads by reflection to multiples of 16, runs the generator of
+    `direction` alone, crops."""
+    y, window = translate_padded(model, architecture, frames, direction, eps, seed, device)
+    return ops.to_display_hw(y, window, uint8=not return_float)
+
+
+# ------------------------------------------------------------------ files
+def discover_inputs(path):
+    """The image files of `path` (one file, or the files of a directory in name order)."""
+    p = Path(path)
+    if p.is_file():
+        return [p]
+    if not p.is_dir():
+        raise FileNotFoundError(f"--input {path}: no such file or directory")
+    return sorted(f for f in p.iterdir() if f.is_file() and f.suffix.lower() in IMAGE_SUFFIXES)
+
+
+def _mode_channels(mode):
+    return {"L": 1, "RGB": 3, "RGBA": 4}.get(mode, 3)
+
+
+def probe(path):
+    """(H, W, C) a file will decode to, from its header."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return im.height, im.width, _mode_channels(im.mode)
+
+
+def decode(path, channels=None):
+    """uint8 (H, W, C): grey stays 1 channel, RGB 3, RGBA 4; every other mode is converted to RGB."""
+    from PIL import Image
+    with Image.open(path) as im:
+        if channels == 3 and im.mode != "RGB" or im.mode not in ("L", "RGB", "RGBA"):
+            im = im.convert("RGB")
+        a = np.asarray(im)
+    return a[:, :, None] if a.ndim == 2 else a
+
+
+def group_by_size(paths, shapes, batch_size):
+    """Batches of at most `batch_size` files of one decoded shape, in order of first appearance: [(shape, [paths])]."""
+    by_shape = {}
+    for p, s in zip(paths, shapes):
+        by_shape.setdefault(tuple(s), []).append(p)
+    return [(s, ps[i:i + batch_size]) for s, ps in by_shape.items() for i in range(0, len(ps), batch_size)]
+
+
+def size_problem(n, h, w):
+    """Why a batch of n frames of h x w cannot be translated, or None."""
+    if h < ops.MIN_TRANSLATE_SIDE or w < ops.MIN_TRANSLATE_SIDE:
+        return f"smaller than {ops.MIN_TRANSLATE_SIDE} on a side"
+    hp, wp, _, _ = ops.pad_plan(h, w)
+    if n * hp * wp > ops.MAX_TRANSLATE_PIXELS:
+        return (f"{n} x {hp}x{wp} padded pixels exceed the bound of {ops.MAX_TRANSLATE_PIXELS} per batch (no tiling: InstanceNorm "
+                f"statistics are per whole image)")
+    return None
+
+
+def output_name(path, suffix="_translated"):
+    return f"{Path(path).stem}{suffix}.png"
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="Translate whole images of any size with a trained generator (MI355X-native path)")
+    p.add_argument("--checkpoint", required=True, help="a run directory (args.json + best_model.pth) or a .pth file")
+    p.add_argument("--input", required=True, help="an image file or a directory of images")
+    p.add_argument("--output", required=True, help="directory the PNGs (and metrics.json) are written to")
+    p.add_argument("--architecture", type=str, default=None, choices=train.REFERENCE_ARCHS + list(train.ALIASES),
+                   help="needed with a bare .pth; overrides args.json otherwise")
+    p.add_argument("--latent_dim", type=int, default=None)
+    p.add_argument("--direction", choices=["a2b", "b2a"], default="a2b",
+                   help="a2b: G; b2a: F of the cycle models.  doubleae / doublevae: translate_A_to_B (decoder_B) / translate_B_to_A "
+                        "(decoder_A) — not the reconstruction test.py shows for them")
+    p.add_argument("--eps", choices=["sample", "mean"], default="sample",
+                   help="variational generators: sample the latent (as test.py does) or decode its mean (deterministic)")
+    p.add_argument("--seed", type=int, default=1234, help="the eps stream of --eps sample")
+    p.add_argument("--batch_size", type=int, default=1, help="frames of equal size are translated together, at most this many")
+    p.add_argument("--size", type=int, default=None,
+                   help="first resize every frame to SIZE x SIZE (the reference's Resize((S, S)); a multiple of 16, at least 32)")
+    p.add_argument("--targets", type=str, default=None,
+                   help="directory with the expected images under the same file names: writes metrics.json (L1, MSE, PSNR, SSIM)")
+    p.add_argument("--suffix", type=str, default="_translated")
+    p.add_argument("--num_workers", type=int, default=4, help="host threads that decode and write images")
+    return p
+
+
+class _PairFiles:
+    """input_pipeline source over (input, target-or-input) files, for --size."""
+
+    def __init__(self, paths, targets):
+        self.paths, self.targets, self.paired = paths, targets, True
+
+    def __len__(self):
+        return len(self.paths)
+
+    def pair(self, idx, rng):
+        x = decode(self.paths[idx], 3)
+        return x, (decode(self.targets[idx], 3) if self.targets else x)
+
+
+def _pinned(shape):
+    return torch.empty(shape, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+
+
+def load_batch(paths, shape, pool):
+    """The files of one batch decoded on the pool's threads into one pinned uint8 (N, H, W, C) buffer."""
+    buf = _pinned((len(paths),) + tuple(shape))
+    view = buf.numpy()
+
+    def one(k):
+        a = decode(paths[k])
+        if a.shape != tuple(shape):
+            raise ValueError(f"{paths[k]}: decoded to {a.shape}, its header said {tuple(shape)}")
+        view[k] = a
+    list(pool.map(one, range(len(paths))))
+    return buf
+
+
+def run_batch(model, architecture, frames, targets, args, device):
+    """One batch on the device: (uint8 (N, H, W, 3) host array of the translated frames, (N, 4) float64 metrics or None)."""
+    y, window = translate_padded(model, architecture, frames, args.direction, args.eps, None, device)
+    metrics = None
+    if targets is not None:
+        t, _ = ops.image_load(targets.to(device, non_blocking=True))
+        metrics = ops.image_metrics_hw(y, t, window).cpu().double().numpy()
+    return ops.to_display_hw(y, window, uint8=True).cpu().numpy(), metrics
+
+
+def run_resized(model, architecture, paths, targets, args, device):
+    """--size: yields (paths of a batch, uint8 results, metrics) with every frame resized to S x S by the evaluator's pipeline."""
+    pipe = input_pipeline.DeviceInputPipeline(_PairFiles(paths, targets), args.batch_size, args.size, device, recipe="test",
+                                              shuffle=False, seed=args.seed, num_workers=max(1, args.num_workers),
+                                              same_xy=targets is None)
+    done = 0
+    for batch in pipe:
+        x = batch["x"]
+        y = run_generator(model, architecture, x, args.direction, args.eps, None)
+        metrics = ops.image_metrics_hw(y, batch["y"]).cpu().double().numpy() if targets is not None else None
+        yield paths[done:done + x.shape[0]], ops.to_display_hw(y, None, uint8=True).cpu().numpy(), metrics
+        done += x.shape[0]
+
+
+def _finite_or_none(v):
+    return float(v) if math.isfinite(v) else None
+
+
+def metrics_report(names, rows):
+    """metrics.json: per file and mean; PSNR is null where MSE is 0 (as in test.py's summary.json)."""
+    per_file = {n: {k: _finite_or_none(float(r[i])) for i, k in enumerate(METRIC_NAMES)} for n, r in zip(names, rows)}
+    a = np.asarray(rows, dtype=np.float64).reshape(-1, 4)
+    mean = {k: _finite_or_none(float(a[:, i].mean())) if len(a) else None for i, k in enumerate(METRIC_NAMES)}
+    return {"num_files": len(names), "mean": mean, "per_file": per_file}
+
+
+def _device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("this path has no CPU implementation: an MI355X is required")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def main(argv=None):
+    """Returns the exit code: 0, or 1 when some frame was skipped (too small, too large, unreadable, no target)."""
+    args = build_parser().parse_args(argv)
+    if args.batch_size < 1:
+        raise ValueError("--batch_size must be at least 1")
+    if args.size is not None and (args.size < ops.MIN_TRANSLATE_SIDE or args.size % 16):
+        raise ValueError(f"--size must be a multiple of 16 and at least {ops.MIN_TRANSLATE_SIDE}")
+    device = _device()
+    model, architecture = load_generator(args.checkpoint, args.architecture, args.latent_dim, None, device)
+    generator_of(model, architecture, args.direction)               # a direction the model does not have: fail before any file
+    paths = discover_inputs(args.input)
+    if not paths:
+        print(f"No images found under {args.input}")
+        return 1
+    out_dir = Path(args.output)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    skipped, target_of = [], {}
+    if args.targets:
+        for p in list(paths):
+            t = Path(args.targets) / p.name
+            if t.is_file():
+                target_of[p] = t
+            else:
+                skipped.append((p, f"no target {t}"))
+                paths.remove(p)
+    ops.manual_seed(args.seed)                                      # one eps stream over the whole folder
+    names, rows, done = [], [], [0]
+    pool = ThreadPoolExecutor(max_workers=max(1, args.num_workers))
+
+    def write(batch_paths, u8, metrics):
+        from PIL import Image
+        list(pool.map(lambda k: Image.fromarray(u8[k]).save(out_dir / output_name(batch_paths[k], args.suffix)),
+                      range(len(batch_paths))))
+        if metrics is not None:
+            names.extend(p.name for p in batch_paths)
+            rows.extend(metrics)
+        for p in batch_paths:
+            print(f"  {p.name} -> {output_name(p, args.suffix)}")
+        done[0] += len(batch_paths)
+
+    if args.size is not None:
+        problem = size_problem(args.batch_size, args.size, args.size)
+        if problem:
+            raise ValueError(f"--size {args.size} with --batch_size {args.batch_size}: {problem}")
+        targets = [target_of[p] for p in paths] if args.targets else None
+        for batch_paths, u8, metrics in run_resized(model, architecture, paths, targets, args, device):
+            write(batch_paths, u8, metrics)
+    else:
+        shapes = []
+        for p in list(paths):
+            try:
+                shapes.append(probe(p))
+            except Exception as e:                                  # not an image, truncated header: reported, the folder goes on
+                skipped.append((p, f"unreadable: {e}"))
+                paths.remove(p)
+        for shape, batch_paths in group_by_size(paths, shapes, args.batch_size):
+            problem = size_problem(len(batch_paths), shape[0], shape[1])
+            if problem:
+                skipped.extend((p, f"{shape[0]}x{shape[1]}: {problem}") for p in batch_paths)
+                continue
+            try:
+                frames = load_batch(batch_paths, shape, pool)
+                targets = None
+                if args.targets:
+                    targets = load_batch([target_of[p] for p in batch_paths], probe(target_of[batch_paths[0]]), pool)
+                    if targets.shape[1:3] != frames.shape[1:3]:
+                        raise ValueError(f"target is {targets.shape[1]}x{targets.shape[2]}, input {shape[0]}x{shape[1]}")
+            except (OSError, ValueError) as e:
+                skipped.extend((p, str(e)) for p in batch_paths)
+                continue
+            u8, metrics = run_batch(model, architecture, frames, targets, args, device)
+            write(batch_paths, u8, metrics)
+    pool.shutdown()
+    if args.targets:
+        with open(out_dir / "metrics.json", "w") as f:
+            json.dump(metrics_report(names, rows), f, indent=2, allow_nan=False)
+        print(f"Saved metrics to: {out_dir / 'metrics.json'}")
+    for p, why in skipped:
+        print(f"Skipped {p}: {why}", file=sys.stderr)
+    print(f"Translated {done[0]} file(s) into {out_dir}"
+          + (f", skipped {len(skipped)}" if skipped else ""))
+    return 1 if skipped else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
