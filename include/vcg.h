@@ -320,7 +320,10 @@ int vcg_image_metrics_hw(const float* out, const float* target, float* result, i
 /* torch.optim.Adam.step — call sites Networks.py:312,894,1928-1935 ---------- */
 /* single-tensor torch formula on one flat buffer:
    m += (1-b1)(g-m); v = b2 v + (1-b2) g^2; p -= step_size * m / (sqrt(v)/bc2_sqrt + eps)
-   one_minus_beta1/2: 1 - beta computed in double by the caller and rounded once, as torch passes them to lerp_ / addcmul_ */
+   one_minus_beta1/2: 1 - beta computed in double by the caller and rounded once, as torch passes them to lerp_ / addcmul_
+   g above is grad[i] * grad_scale (1 / world after a summing all-reduce).  Where that product is not exact in fp32 it enters m
+   through one FMA and v through a double evaluation rounded once, so that v stays within 3 units of fp32 roundoff of the formula;
+   for grad_scale 1 or a power of two the result is torch's fp32 sequence bit for bit. */
 int vcg_adam_step(float* p, const float* g, float* m, float* v, size_t n,
                   float step_size, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
                   float eps, float bc2_sqrt, float grad_scale, void* stream);

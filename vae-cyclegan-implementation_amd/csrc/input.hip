@@ -123,9 +123,14 @@ __global__ __launch_bounds__(256) void k_input_resample(ResampleP p) {
 // Pillow RGB -> L
 __device__ __forceinline__ int pil_L(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
 // Image.blend(degenerate, image, alpha) for one channel: C float  t = in1 + alpha * (in2 - in1),  truncated; clipped when alpha
-// is outside [0, 1] (Blend.c).  __fmul_rn / __fadd_rn: no fused multiply-add, as the C compiled for plain x86-64.
+// is outside [0, 1] (Blend.c).  No fused multiply-add, as the C compiled for plain x86-64: the product is rounded before the
+// sum.  __fmul_rn / __fadd_rn do not keep the compiler from contracting the two into one v_fma_f32 (they are a plain * and +);
+// the empty asm makes the rounded product opaque to it.  With alpha = 1.6 a fused blend lands on another level for 4 % of all
+// RGB triples (tests/test_gpu_input_rng_adam.py, saturation 1.6).
 __device__ __forceinline__ int pil_blend1(int deg, int v, float alpha, bool interp) {
-  const float t = __fadd_rn((float)deg, __fmul_rn(alpha, (float)(v - deg)));
+  float prod = __fmul_rn(alpha, (float)(v - deg));
+  asm volatile("" : "+v"(prod));
+  const float t = __fadd_rn((float)deg, prod);
   if (interp) return (int)t & 255;                               // (UINT8)(float): truncation (0 <= t <= 255 here)
   return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
 }
@@ -260,8 +265,11 @@ __global__ __launch_bounds__(256) void k_u8_to_f4(const unsigned char* __restric
   const unsigned char* src = arena + (((size_t)(uint32_t)q[1]) << 32 | (size_t)(uint32_t)q[0]);
   float4* dst = fbuf + (((size_t)(uint32_t)q[4]) << 32 | (size_t)(uint32_t)q[3]);
   const int npx = q[2];
+  // ToTensor DIVIDES: v * (1.f / 255.f) is one ulp off v / 255 for 126 byte values, and a frame whose jitter is disabled keeps
+  // what is stored here (a jittered one is put back on the uint8 grid and divided by k_color_jitter)
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += gridDim.x * blockDim.x)
-    dst[i] = make_float4(src[3 * (size_t)i] * (1.f / 255.f), src[3 * (size_t)i + 1] * (1.f / 255.f), src[3 * (size_t)i + 2] * (1.f / 255.f), 0.f);
+    dst[i] = make_float4(__fdiv_rn((float)src[3 * (size_t)i], 255.f), __fdiv_rn((float)src[3 * (size_t)i + 1], 255.f),
+                         __fdiv_rn((float)src[3 * (size_t)i + 2], 255.f), 0.f);
 }
 
 // ColorJitter on whole decoded frames, before any crop (hypersim's colour modality): unpack + jitter; the resample then reads

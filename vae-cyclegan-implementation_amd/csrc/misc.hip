@@ -761,6 +761,20 @@ extern "C" int vcg_fullmap_wgrad(const float* g, const float* x, const float* ws
 //   exp_avg.lerp_(grad, 1-beta1); exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
 //   denom = exp_avg_sq.sqrt() / bias_correction2_sqrt + eps; param.addcdiv_(exp_avg, denom, value=-step_size)
 // One launch over the model's flat parameter buffer: 28 B/param of HBM traffic, float4 per lane.
+// exp_avg_sq' = beta2 v + (1 - beta2) (g grad_scale)^2.  gg = g * grad_scale is rounded to fp32 (torch is handed the rounded product
+// too), and squaring doubles that rounding: with grad_scale = 1/3 the fp32 formula ends 3.6 U off the exact one.  Where the product
+// was rounded at all (ge, its exact rounding error from one FMA, is not 0 — never for grad_scale 1 or a power of two) the update is
+// evaluated in double from the unrounded product and rounded once; elsewhere it is the fp32 formula, bit for bit what it always was.
+// exp_avg takes g grad_scale - m from one FMA: the product is not rounded on its way in (for grad_scale 1 or a power of two the same
+// bits as gg - m).
+__device__ __forceinline__ float adam_v(float v, float g, float gscale, float gg, float b2, float w2) {
+  const float ge = fmaf(g, gscale, -gg);
+  if (ge != 0.f) {
+    const double gd = (double)g * (double)gscale;
+    return (float)((double)v * (double)b2 + (double)w2 * gd * gd);
+  }
+  return v * b2 + w2 * gg * gg;
+}
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g,
                                               float* __restrict__ m, float* __restrict__ v, size_t n,
                                               float step_size, float b2, float w1, float w2, float eps, float bc2_sqrt,
@@ -776,8 +790,8 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
 #define ADAM1(c)                                         \
     {                                                    \
       float gg = gv.c * gscale;                          \
-      mv.c = mv.c + w1 * (gg - mv.c);                    \
-      vv.c = vv.c * b2 + w2 * gg * gg;                   \
+      mv.c = mv.c + w1 * fmaf(gv.c, gscale, -mv.c);      \
+      vv.c = adam_v(vv.c, gv.c, gscale, gg, b2, w2);     \
       float den = sqrtf(vv.c) / bc2_sqrt + eps;          \
       pv.c = pv.c - step_size * (mv.c / den);            \
     }
@@ -789,8 +803,8 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
   if (blockIdx.x == 0)
     for (size_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) {
       float gg = g[i] * gscale;
-      float mm = m[i] + w1 * (gg - m[i]);
-      float vv = v[i] * b2 + w2 * gg * gg;
+      float mm = m[i] + w1 * fmaf(g[i], gscale, -m[i]);
+      float vv = adam_v(v[i], g[i], gscale, gg, b2, w2);
       float den = sqrtf(vv) / bc2_sqrt + eps;
       p[i] = p[i] - step_size * (mm / den);
       m[i] = mm;

@@ -903,6 +903,16 @@ _TICKETS = []          # draw positions handed out ahead of time (eps_tickets), 
 _FORCED_OFFSETS = []
 
 
+def _eps_count(shape):
+    """Values one reparameterisation of a logical NCHW `shape` draws: _ReparamFn draws for the PHYSICAL buffer (channel pitch a
+    multiple of 4), so a reservation made from the logical count would be too short whenever latent_dim % 4 != 0 and the next
+    reserved draw would repeat part of this one."""
+    n = 1
+    for s in shape:
+        n *= s
+    return n // shape[1] * pitch(shape[1]) if len(shape) == 4 else n
+
+
 def eps_tickets(plan, device):
     """Reserve the eps draws of several reparameterisations in the REFERENCE's call order, to be used in another one (the two
     directions of a cycle model are issued interleaved on two streams).  `plan`: [(shape, skip)]; returns one ticket per entry
@@ -919,9 +929,7 @@ def eps_tickets(plan, device):
                 raise RuntimeError(f"injected eps has shape {tuple(e.shape)}, expected {tuple(shape)}")
             out.append(("tensor", e))
         else:
-            n = 1
-            for s_ in shape:
-                n *= s_
+            n = _eps_count(shape)
             off = _RNG["offset"]
             _RNG["offset"] += (n + 3) // 4
             out.append(None if skip else ("offset", off))
@@ -965,10 +973,7 @@ def next_eps(shape, device, skip=False):
             raise RuntimeError(f"injected eps has shape {tuple(e.shape)}, expected {tuple(shape)}")
         return to_nhwc(e.to(device))
     if skip:
-        n = 1
-        for s in shape:
-            n *= s
-        _RNG["offset"] += (n + 3) // 4
+        _RNG["offset"] += (_eps_count(shape) + 3) // 4
     return None
 
 
@@ -997,6 +1002,7 @@ class _ReparamFn(torch.autograd.Function):
                                               _RNG["seed"], off, _stream()), "vcg_reparam_fwd")
         ctx.save_for_backward(epsp, lvp)
         c = mu.shape[1]
+        ctx.c_logical = c
         return logical_of(z, c), logical_of(lvc, c)
 
     @staticmethod
@@ -1009,7 +1015,7 @@ class _ReparamFn(torch.autograd.Function):
         dlv = torch.empty_like(lvp)
         _native.check(lib.vcg_reparam_bwd(_ptr(gzp), _ptr(glp), _ptr(epsp), _ptr(lvp), _ptr(dmu), _ptr(dlv),
                                           lvp.numel(), _stream()), "vcg_reparam_bwd")
-        c = lvp.shape[3]
+        c = ctx.c_logical            # lvp.shape[3] is the channel PITCH: 8 for latent_dim 6, and autograd refuses that gradient
         return logical_of(dmu, c), logical_of(dlv, c), None
 
 
