@@ -25,9 +25,7 @@ that CASES below still reach every branch of this table:
                  <64,64>, split<64>, split<128> (<64,128> is a candidate of gemm_plan, not of wgrad_plan); <= 24 and > 24 parts (k_slab_sum); k_wgrad_scatter,
                  k_wgrad_scatter_swapped and k_wgrad_reduce; bias column sums with gbias given and NULL, and cout_log < Cout
 
-Out of scope: branches that only an environment switch reaches (VCG_SLAB=0, VCG_RING=0, VCG_THININ=2, VCG_WINO_PLANES=0,
-VCG_WGRAD_TR=0/1, VCG_GEMM_DMA=0, VCG_IN_TAIL=1, the VCG_WINO_GATE_* and VCG_PLAN_TSCALE overrides) and anything under -DVCG_STAMP;
-the mirror assumes the defaults.
+Out of scope: anything under -DVCG_STAMP.
 
 What each GPU case checks, for the forward, the forward with statistics, the data gradient and the weight gradient:
   * every element against a float64 reference of the same operation (reflect or zero padding, PixelUnshuffle folded in the
@@ -129,7 +127,7 @@ def _fold_planes_floats(kh, c):
 
 
 def thinin_fwd_ok(g):
-    disc = g["KH"] == 4 and g["KW"] == 4 and g["stride"] == 2 and g["pad"] == 1          # the 7x7 stem form needs VCG_THININ=2
+    disc = g["KH"] == 4 and g["KW"] == 4 and g["stride"] == 2 and g["pad"] == 1
     return (disc and g["ups"] == 1 and g["Cin"] == 4 and g["Cout"] == 64 and g["Ho"] % 16 == 0 and g["Wo"] % 16 == 0
             and (not g["reflect"] or (g["H"] > g["pad"] + 8 and g["W"] > g["pad"] + 8)))
 

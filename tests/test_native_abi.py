@@ -119,7 +119,7 @@ def test_launch_plans_are_host_side_and_consistent(pkg):
         per = (nwg + 15) // 16
         return (sub * nwg + sub * ((nwg + per - 1) // per)) * nr * 64 * f4 + 256
     assert 0 <= lib.vcg_conv_wgrad_workspace(u4) - (ring_ws(8, 256, 256, 288) + 255) // 256 * 256 <= 1 << 20     # + bias column sums
-    # the latent convs 1024 -> 64: Kc Cout / (Kc + Cout) = 60 is under every Winograd gate (forward 64, data gradient 80):
+    # the latent convs 1024 -> 64: Kc Cout / (Kc + Cout) = 60 is under every Winograd gate (forward 100, data gradient 80):
     # no transformed copies, the planes of the direct split-operand kernels instead
     mu = _desc(8, 16, 16, 1024, 64, 3)
     assert lib.vcg_pack_weight_floats(mu) == 9 * 1024 * 64 + 64 * (9216 // 32) * 32 + 9 * 1024 * 2 * 32 + 16
@@ -214,3 +214,46 @@ def test_conv_plan_mirror_matches_the_library_and_cases_hit_every_branch(pkg):
         hit |= branch_labels(case_desc(c), c[2])
     missing = [r for r in REQUIRED if r not in hit]
     assert not missing, f"no convolution case reaches: {missing}"
+
+
+# what a child process prints: the host-side sizes of every descriptor it is given, then vcg_in_workspace of three shapes
+_SIZES_CHILD = r"""
+import ctypes, json, sys
+lib = ctypes.CDLL(sys.argv[1])
+job = json.load(sys.stdin)
+for name in ("vcg_pack_weight_floats", "vcg_conv_fwd_workspace", "vcg_conv_dgrad_workspace", "vcg_conv_wgrad_workspace",
+             "vcg_conv_saved_floats", "vcg_in_workspace"):
+    getattr(lib, name).restype = ctypes.c_size_t
+lib.vcg_conv_reads_wf.restype = ctypes.c_int
+lib.vcg_in_workspace.argtypes = [ctypes.c_int] * 3
+for d in job["descs"]:
+    cd = (ctypes.c_int32 * 16)(*d)
+    print(d[:14], lib.vcg_pack_weight_floats(cd), lib.vcg_conv_fwd_workspace(cd), lib.vcg_conv_dgrad_workspace(cd),
+          lib.vcg_conv_wgrad_workspace(cd), lib.vcg_conv_saved_floats(cd), lib.vcg_conv_reads_wf(cd))
+for n, hw, c in job["norms"]:
+    print("in", n, hw, c, lib.vcg_in_workspace(n, hw, c))
+"""
+# the kernel-variant switches libvcg.so once read, each at its former non-default value
+_RETIRED_SWITCHES = dict(VCG_GEMM_DMA="0", VCG_GEMM_SPREAD="0", VCG_GEMM_SHAPE="32", VCG_GEMM_STAGGER="0", VCG_WINO_PLANES="0",
+                         VCG_WINO_GATE_F="1", VCG_WINO_GATE_D="1", VCG_WINO_GATE_W="1", VCG_WGRAD_TR="0", VCG_IN_TAIL="1",
+                         VCG_IN_BWD_FLAT="1", VCG_THININ="2", VCG_PLAN_TSCALE="0.25", VCG_SLAB="0", VCG_RING="0")
+
+
+def test_library_ignores_environment(pkg):
+    """libvcg.so reads no environment variable: two fresh processes, one with none of the retired kernel-variant switches set and
+    one with every one of them at its former non-default value, report the same pack, workspace and saved sizes for every
+    descriptor of the convolution case list and the same InstanceNorm workspaces (the Winograd gates, the slab switch and the
+    thin-input mode all used to move these numbers)."""
+    import json
+    import sys
+    from test_gpu_conv_plans import CASES, case_desc
+    path = pkg._native.build()
+    job = json.dumps({"descs": [list(case_desc(c)) for c in CASES], "norms": [(8, 256 * 256, 64), (8, 16 * 16, 1024), (3, 33 * 17, 36)]})
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("VCG_")}
+    outs = []
+    for env in (clean, dict(clean, **_RETIRED_SWITCHES)):
+        res = subprocess.run([sys.executable, "-c", _SIZES_CHILD, path], input=job, env=env, capture_output=True, text=True, timeout=120)
+        assert res.returncode == 0, res.stderr
+        outs.append(res.stdout)
+    assert len(outs[0].splitlines()) == len(CASES) + 3
+    assert outs[0] == outs[1]

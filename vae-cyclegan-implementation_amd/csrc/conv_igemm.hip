@@ -24,7 +24,9 @@
 //             blockIdx.z into fp32 slabs that a second kernel sums in a fixed order
 //             (bitwise reproducible, no float atomics) and scatters to OIHW.
 #include "vcg_common.h"
+#ifdef VCG_STAMP
 #include <stdlib.h>
+#endif
 
 struct ConvP {
   const float* a;
@@ -61,7 +63,6 @@ struct ConvP {
   // channel, as chunk `(m0 % HoWo) / 128` of image `m0 / HoWo` in the [N][nchunk][Cout][2] double partials of norm.hip
   double* in_part;
   int in_nchunk;
-  VcgInTail in_tail;             // ... and the last tile of an (image, column tile) combines them into mean / rstd (vcg_common.h)
   // fp16 x 2 split-operand kernels (vcg_common.h): the largest magnitude of the tensor behind `a` and of the one behind `b`
   VcgAmax amax_a, amax_b;
   // batched Winograd weight gradient: `a` (the kept V) is pre-split planes [batch][T][K / 32][2][32] (k_wino_in_planes), not fp32
@@ -657,14 +658,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_fwd_split(ConvP p) {
       const uint32_t n = fd_div((uint32_t)m0, p.fd_howo);
       const uint32_t chunk = ((uint32_t)m0 - n * (uint32_t)(p.Ho * p.Wo)) / BM;
       double* o = p.in_part + (((size_t)n * p.in_nchunk + chunk) * p.Cout + n0 + tid) * 2;
-      vcg_store_sc1(o, red[tid * 2] + red[(BN + tid) * 2]);
-      vcg_store_sc1(o + 1, red[tid * 2 + 1] + red[(BN + tid) * 2 + 1]);
-    }
-    if (p.in_tail.out1) {
-      const uint32_t n = fd_div((uint32_t)m0, p.fd_howo);
-      __syncthreads();                // `red` (As) has been read
-      vcg_in_tail_run<0>(p.in_tail, p.in_part, (int)n, n0, BN, p.Cout, p.in_nchunk, p.in_tail.counters + n * gridDim.y + nt,
-                         (uint32_t)p.in_nchunk, reinterpret_cast<double*>(&As[0][0]));
+      o[0] = red[tid * 2] + red[(BN + tid) * 2];
+      o[1] = red[tid * 2 + 1] + red[(BN + tid) * 2 + 1];
     }
   }
   VCG_STAMP_AT(3);
@@ -1872,13 +1867,9 @@ __global__ __launch_bounds__(256) void k_pack_planes(const float* __restrict__ w
 
 // gbias[co] += sum_m dy[m][co]: per-chunk partials then a fixed-order final sum
 // float4 per lane (TC channel quads x TP row lanes per block), 4 independent rows in flight per lane
-// The last chunk block of a channel group (arrival counter `ctr`, vcg_common.h / VcgInTail) sums the group's chunk partials
-// in a fixed order and adds them to gbias: no separate finalize launch.  ctr == null: the caller runs k_colsum_final.
 __global__ __launch_bounds__(256) void k_colsum_partial(const float* __restrict__ dy, float* __restrict__ part,
-                                                        int M, int C, int rows_per_chunk, int TC, uint32_t* ctr,
-                                                        float* __restrict__ gbias, int c_log) {
+                                                        int M, int C, int rows_per_chunk, int TC) {
   __shared__ float4 red[256];
-  __shared__ int last;
   const int TP = 256 / TC;
   const int tc = threadIdx.x % TC, tp = threadIdx.x / TC;
   const int c4 = blockIdx.x * TC + tc;
@@ -1902,35 +1893,8 @@ __global__ __launch_bounds__(256) void k_colsum_partial(const float* __restrict_
   if (tp == 0 && c4 * 4 < C) {
     for (int k = 1; k < TP; ++k) f4add(s, red[k * TC + tc]);
     float* o = part + (size_t)blockIdx.y * C + c4 * 4;
-    vcg_store_sc1_f2(o, s.x, s.y);
-    vcg_store_sc1_f2(o + 2, s.z, s.w);
-  }
-  if (!ctr) return;
-  if (!vcg_last_arrival(ctr + blockIdx.x, gridDim.y, &last)) return;
-  // thread (tc, tp): channel quad tc, chunks tp, tp + TP, ... — four loads in flight — then the TP lanes in order
-  const int nchunk = (int)gridDim.y;
-  float4 t0 = f4zero(), t1 = t0, t2 = t0, t3 = t0;
-  if (c4 * 4 < C) {
-    const float* base = part + (size_t)c4 * 4;
-    int k = tp;
-    auto ld = [](const float* q) { const float2 lo = vcg_load_sc1_f2(q), hi = vcg_load_sc1_f2(q + 2); return make_float4(lo.x, lo.y, hi.x, hi.y); };
-    for (; k + 3 * TP < nchunk; k += 4 * TP) {
-      const float4 v0 = ld(base + (size_t)k * C), v1 = ld(base + (size_t)(k + TP) * C);
-      const float4 v2 = ld(base + (size_t)(k + 2 * TP) * C), v3 = ld(base + (size_t)(k + 3 * TP) * C);
-      f4add(t0, v0); f4add(t1, v1); f4add(t2, v2); f4add(t3, v3);
-    }
-    for (; k < nchunk; k += TP) f4add(t0, ld(base + (size_t)k * C));
-    f4add(t0, t1); f4add(t2, t3); f4add(t0, t2);
-  }
-  red[threadIdx.x] = t0;
-  __syncthreads();
-  if (tp == 0 && c4 * 4 < C) {
-    for (int k = 1; k < TP; ++k) f4add(t0, red[k * TC + tc]);
-    const int c = c4 * 4;
-    if (c + 0 < c_log) gbias[c + 0] += t0.x;
-    if (c + 1 < c_log) gbias[c + 1] += t0.y;
-    if (c + 2 < c_log) gbias[c + 2] += t0.z;
-    if (c + 3 < c_log) gbias[c + 3] += t0.w;
+    *reinterpret_cast<float2*>(o) = make_float2(s.x, s.y);             // (o is 8-byte aligned)
+    *reinterpret_cast<float2*>(o + 2) = make_float2(s.z, s.w);
   }
 }
 // 8 channels x 32 chunk lanes per block: the loop over chunk partials is a dependent chain of L2 round trips
@@ -2016,7 +1980,7 @@ static void fill_params(const ConvGeom& g, ConvP& p) {
   p.ksplit = 1; p.kt_per = 0; p.slab = nullptr; p.adjoint = 0; p.src_pitch = g.Cout;
   p.a_bytes = p.b_bytes = 0; p.dbl_mirror = 0;
   p.bias = nullptr;
-  p.in_part = nullptr; p.in_nchunk = 0; p.in_tail = vcg_in_tail_none();
+  p.in_part = nullptr; p.in_nchunk = 0;
   p.amax_a = p.amax_b = vcg_amax_const(0);      // scale 1 (the fp32-MFMA kernels never look)
   p.a_planes = 0;
 }
@@ -2025,12 +1989,6 @@ static void fill_params(const ConvGeom& g, ConvP& p) {
 // exists, use it.  Otherwise (deep layers: M = N*16*16 pixels, K up to 18 432) keep the big, efficient
 // tile and slice K across blockIdx.z instead of shrinking the tile: partial tiles go to fp32 slabs that
 // k_splitk_finish sums in a fixed order (+ bias + activation).
-// VCG_PLAN_TSCALE: multiplies the planners' time per K-step (their constants were measured on the fp32-MFMA kernels of round 1;
-// the fp16 x 2 kernels step ~2x faster while a K slice's slab traffic and finish launch cost what they did) — A/B measurements
-static double plan_tscale() {
-  static const double v = [] { const char* e = getenv("VCG_PLAN_TSCALE"); return e ? atof(e) : 1.0; }();
-  return v;
-}
 static void gemm_plan(long long rows, long long cols, int nkt, bool allow_split, int& bm, int& bn, int& nsplit,
                       int& kt_per, int batches = 1, bool allow_bn32 = false, bool single_level = false) {
   // cost model (us): rounds of resident workgroups x K-steps per workgroup x time per K-step of that tile,
@@ -2054,7 +2012,7 @@ static void gemm_plan(long long rows, long long cols, int nkt, bool allow_split,
       if (ns > 1 && kt < 8) break;
       int real_ns = (nkt + kt - 1) / kt;
       long long rounds = (tiles * real_ns + slots - 1) / slots;
-      double t = rounds * kt * c.t_step * plan_tscale();
+      double t = rounds * kt * c.t_step;
       if (real_ns > 1) t += (double)real_ns * rows * cols * 8.0 / 3.0e6 + 3.0;   // + one more launch
       if (t < best * 0.97) { best = t; bm = c.bm; bn = c.bn; nsplit = real_ns; kt_per = kt; }
     }
@@ -2113,16 +2071,16 @@ static size_t wf_floats(const ConvGeom& g) { return (((size_t)g.K * g.Cout + 63)
 // gradient the WFD planes.  Layers that own Winograd copies (every D, R and U block from 128 reduction channels on) run
 // through those in all three directions and get neither; should one of them meet a map Winograd cannot take (odd sizes), it
 // runs on the fp32-MFMA kernels from Wf.  Thin (Cout == 4) layers and the kw-folded data gradient never take them either.
-// (a layer with Winograd copies whose channel product is under a direction's gate — conv_wino.hip: forward from
-// Kc Cout / (Kc + Cout) = 64, data gradient from 80; the 1024 -> 64 latent convs sit at 60 — runs that direction direct, and
-// gets the planes for it)
+// (a layer with Winograd copies whose channel product is under a direction's gate — kWinoGateFwd / kWinoGateDgrad, vcg_common.h:
+// forward from Kc Cout / (Kc + Cout) = 100, data gradient from 80; the 1024 -> 64 latent convs sit at 60 — runs that direction
+// direct, and gets the planes for it)
 static bool wino_takes_fwd(const ConvGeom& g) {
   const long long kc = (long long)g.ups * g.ups * g.Cin;
-  return vcg_wino_weight_ok(g) && kc * g.Cout >= vcg_wino_gate_fwd() * (kc + g.Cout);
+  return vcg_wino_weight_ok(g) && kc * g.Cout >= kWinoGateFwd * (kc + g.Cout);
 }
 static bool wino_takes_dgrad(const ConvGeom& g) {
   const long long kc = (long long)g.ups * g.ups * g.Cin;
-  return vcg_wino_weight_ok(g) && kc * g.Cout >= vcg_wino_gate_dgrad() * (kc + g.Cout);
+  return vcg_wino_weight_ok(g) && kc * g.Cout >= kWinoGateDgrad * (kc + g.Cout);
 }
 // floats of the Winograd copies a layer keeps: U if some map can take the forward (and with it the weight gradient), Ud if
 // some map can take the data gradient
@@ -2145,21 +2103,14 @@ static size_t wfd_offset(const ConvGeom& g) { return wft_offset(g) + (wft_wanted
 // the pack was scaled by: vcg_common.h), read by the kernels that multiply by those planes
 static size_t wamax_offset(const ConvGeom& g) { return wfd_offset(g) + (wfd_wanted(g) ? wfd_floats(g) : 0); }
 const void* vcg_pack_amax(const ConvGeom& g, const float* wf) { return wf + wamax_offset(g); }
-// VCG_SLAB=0 keeps the slab kernels (conv_slab.hip) out of the dispatch: A/B measurements only
-static bool slab_enabled() {
-  static const int on = [] { const char* e = getenv("VCG_SLAB"); return e ? atoi(e) : 1; }();
-  return on != 0;
-}
-// VCG_RING=0: the row-ring weight gradients (conv_ring.hip) out of the dispatch
-static bool wgrad_ring_ok(const ConvGeom& g) {
-  static const int on = [] { const char* e = getenv("VCG_RING"); return e ? atoi(e) : 1; }();
-  return on != 0 && !vcg_wino_wgrad_ok(g) && vcg_ring_wgrad_ok(g);
-}
+// the row-ring weight gradients (conv_ring.hip)
+static bool wgrad_ring_ok(const ConvGeom& g) { return !vcg_wino_wgrad_ok(g) && vcg_ring_wgrad_ok(g); }
+// the slab kernels (conv_slab.hip)
 static bool fwd_slab_ok(const ConvGeom& g) {
-  return slab_enabled() && !vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && !vcg_wino_fwd_ok(g) && wft_wanted(g) && vcg_slab_fwd_ok(g);
+  return !vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && !vcg_wino_fwd_ok(g) && wft_wanted(g) && vcg_slab_fwd_ok(g);
 }
 static bool dgrad_slab_ok(const ConvGeom& g) {
-  return slab_enabled() && !vcg_thin_fold_dgrad_ok(g) && !vcg_thin_dgrad_ok(g) && !vcg_wino_dgrad_ok(g) && wfd_wanted(g) && vcg_slab_dgrad_ok(g);
+  return !vcg_thin_fold_dgrad_ok(g) && !vcg_thin_dgrad_ok(g) && !vcg_wino_dgrad_ok(g) && wfd_wanted(g) && vcg_slab_dgrad_ok(g);
 }
 
 // the forward kernel on a caller-built geometry (no bias, no activation, no K slicing): conv_thin.hip's kw-folded path
@@ -2278,7 +2229,7 @@ static bool fwd_tile_stats_ok(const ConvGeom& g) {
 // in_part != nullptr: also leave the InstanceNorm chunk partials of y there (the caller checked that this launch plan
 // can: Winograd, or fwd_tile_stats_ok) and report the chunk count per image.
 static int conv_fwd_impl(const float* x, const float* wf, const float* bias, float* y, const int32_t* cd, void* ws,
-                         size_t ws_bytes, void* stream, double* in_part, const VcgInTail* tail_req, float* saved = nullptr,
+                         size_t ws_bytes, void* stream, double* in_part, const VcgInStatsOut* stats, float* saved = nullptr,
                          const VcgPre* pre = nullptr) {
   const uint64_t x_handle = vcg_take_hint_x();              // vcg_amax_hint: who wrote x left its largest magnitude (or 0)
   (void)vcg_take_hint_dy();
@@ -2286,22 +2237,21 @@ static int conv_fwd_impl(const float* x, const float* wf, const float* bias, flo
   if (vcg_conv_geom(cd, &g, "vcg_conv_fwd")) return -1;
   VCG_CHECK_ARG(x && wf && y, "vcg_conv_fwd: null pointer");
   if (pre && pre->mean)
-    VCG_CHECK_ARG(!vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && vcg_wino_pre_ok(g),
+    VCG_CHECK_ARG(!vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && vcg_wino_fwd_ok(g),
                   "vcg_conv_fwd_in_pre: this geometry has no normalising gather (ask vcg_conv_pre_ok first)");
   if (vcg_thin_fold_ok(g)) return vcg_thin_fold_fwd(g, x, wf + wf_floats(g), vcg_pack_amax(g, wf), bias, y, ws, ws_bytes, (hipStream_t)stream, x_handle);
   if (vcg_thin_fwd_ok(g)) return vcg_thin_fwd(g, x, wf, bias, y, (hipStream_t)stream);
   if (vcg_thinin_fwd_ok(g)) {
     if (vcg_thinin_fwd(g, x, wf, vcg_pack_amax(g, wf), bias, y, in_part, (hipStream_t)stream, x_handle)) return -2;
     if (in_part)
-      return vcg_in_finalize(in_part, tail_req->out1, tail_req->out2, g.N, tail_req->HW, g.Cout, vcg_thinin_nchunk(g), tail_req->eps,
-                             (hipStream_t)stream);
+      return vcg_in_finalize(in_part, stats->mean, stats->rstd, g.N, stats->HW, g.Cout, vcg_thinin_nchunk(g), stats->eps, (hipStream_t)stream);
     return 0;
   }
   if (vcg_wino_fwd_ok(g))
-    return vcg_wino_fwd(g, x, wf + wf_floats(g), vcg_pack_amax(g, wf), bias, y, ws, ws_bytes, (hipStream_t)stream, in_part, tail_req, saved, x_handle,
+    return vcg_wino_fwd(g, x, wf + wf_floats(g), vcg_pack_amax(g, wf), bias, y, ws, ws_bytes, (hipStream_t)stream, in_part, stats, saved, x_handle,
                         pre);
   if (fwd_slab_ok(g))
-    return vcg_slab_fwd(g, x, wf + wft_offset(g), wft_floats(g) * 4, vcg_pack_amax(g, wf), bias, y, in_part, tail_req, (hipStream_t)stream, x_handle);
+    return vcg_slab_fwd(g, x, wf + wft_offset(g), wft_floats(g) * 4, vcg_pack_amax(g, wf), bias, y, in_part, stats, (hipStream_t)stream, x_handle);
   ConvP p; fill_params(g, p);
   if (in_part) {
     p.in_part = in_part;
@@ -2328,7 +2278,6 @@ static int conv_fwd_impl(const float* x, const float* wf, const float* bias, flo
     // the input's largest magnitude (its scale, vcg_common.h): from its writer's handle, else measured
     if (vcg_operand_amax(x, (size_t)g.N * g.H * g.W * g.Cin, x_handle, 0, st, &p.amax_a)) return -2;
     p.amax_b = vcg_amax_stored(vcg_pack_amax(g, wf));
-    if (in_part) p.in_tail = vcg_in_tail_make(tail_req->out1, tail_req->out2, g.N * (int)grid.y, tail_req->HW, tail_req->eps);
     VcgProfScope prof(bn == 128 ? "k_conv_fwd_split<128>" : "k_conv_fwd_split<64>", gemm_flops, st);
     if (bn == 128) hipLaunchKernelGGL((k_conv_fwd_split<128>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((k_conv_fwd_split<64>), grid, dim3(256), 0, st, p);
@@ -2341,8 +2290,7 @@ static int conv_fwd_impl(const float* x, const float* wf, const float* bias, flo
     hipLaunchKernelGGL(k_splitk_finish, dim3(ew_grid((size_t)g.M * g.Cout / 4)), dim3(256), 0, st, (const float*)ws, bias,
                        y, (size_t)g.M, g.Cout, nsplit, g.cout_log, g.act);
   VCG_LAUNCH_CHECK("vcg_conv_fwd");
-  if (in_part && !p.in_tail.out1)
-    return vcg_in_finalize(in_part, tail_req->out1, tail_req->out2, g.N, tail_req->HW, g.Cout, p.in_nchunk, tail_req->eps, st);
+  if (in_part) return vcg_in_finalize(in_part, stats->mean, stats->rstd, g.N, stats->HW, g.Cout, p.in_nchunk, stats->eps, st);
   return 0;
 }
 
@@ -2389,7 +2337,7 @@ extern "C" int vcg_conv_fwd_in(const float* x, const float* wf, const float* bia
 extern "C" int vcg_conv_pre_ok(const int32_t* cd) {
   ConvGeom g;
   if (vcg_conv_geom(cd, &g, "vcg_conv_pre_ok")) return 0;
-  return (!vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && vcg_wino_pre_ok(g)) ? 1 : 0;
+  return (!vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && vcg_wino_fwd_ok(g)) ? 1 : 0;
 }
 extern "C" int vcg_conv_fwd_in_pre(const float* t_prev, const float* pre_mean, const float* pre_rstd, int pre_act, const float* wf,
                                    const float* bias, float* y, float* mean, float* rstd, float eps, float* saved, const int32_t* cd,
@@ -2416,10 +2364,9 @@ static int conv_fwd_in_impl(const float* x, const float* wf, const float* bias, 
   double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + cws);
   const bool thinin = !vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && vcg_thinin_fwd_ok(g);
   const bool fused = thinin || vcg_wino_fwd_ok(g) || (fwd_slab_ok(g) && vcg_slab_fwd_stats_ok(g)) || fwd_tile_stats_ok(g);
-  // fused: the conv's epilogue leaves the partials and its last block per (image, channel range) finalizes them
-  VcgInTail req = vcg_in_tail_none();
-  req.out1 = mean; req.out2 = rstd; req.HW = g.Ho * g.Wo; req.eps = eps;
-  if (conv_fwd_impl(x, wf, bias, y, cd, ws, cws, stream, fused ? part : nullptr, &req, saved, pre)) return -1;
+  // fused: the conv's epilogue leaves the partials, and vcg_in_finalize behind it combines them into mean / rstd
+  const VcgInStatsOut stats = {mean, rstd, g.Ho * g.Wo, eps};
+  if (conv_fwd_impl(x, wf, bias, y, cd, ws, cws, stream, fused ? part : nullptr, &stats, saved, pre)) return -1;
   if (fused) return 0;
   return vcg_in_stats_pass(y, mean, rstd, g.N, g.Ho * g.Wo, g.Cout, eps, part, ws_bytes - cws, (hipStream_t)stream);
 }
@@ -2599,8 +2546,7 @@ static const int kMaxDirectSlabs = 24;
 static void colsum_plan(const ConvGeom& g, int& tc, int& cgroups, int& rows, int& nchunk) {
   int c4 = g.Cout / 4;
   tc = 1;
-  const int cap = vcg_in_tail_enabled() ? 16 : 256;    // tails on: <= 64 channels per workgroup, so the finalizing workgroup has >= 16 chunk lanes per quad
-  while (tc * 2 <= c4 && tc * 2 <= cap) tc *= 2;
+  while (tc * 2 <= c4 && tc * 2 <= 256) tc *= 2;
   cgroups = (c4 + tc - 1) / tc;
   int tp = 256 / tc;
   long long want = 512 / cgroups;
@@ -2630,7 +2576,7 @@ size_t vcg_wino_wgrad_core_workspace(const ConvGeom& g, int T) {
   return (size_t)wp.parts * 16 * q.K * q.Cout * sizeof(float) + 256;
 }
 int vcg_wino_wgrad_core(const ConvGeom& g, const float* V, const float* dM, int T, float* gw_oihw, void* ws, size_t ws_bytes,
-                        hipStream_t st, const VcgAmax& amax_v, const VcgAmax& amax_dm, bool v_planes) {
+                        hipStream_t st, const VcgAmax& amax_v, const VcgAmax& amax_dm) {
   const ConvGeom q = wino_gemm_geom(g, T);
   const WgradPlan wp = wgrad_plan(q, 16);
   VCG_CHECK_ARG(wp.grid > 0, "vcg_conv_wgrad: no launch plan for the Winograd path");
@@ -2638,8 +2584,8 @@ int vcg_wino_wgrad_core(const ConvGeom& g, const float* V, const float* dM, int 
   ConvP p; fill_params(q, p);
   p.a = V; p.b = dM; p.out = (float*)ws;
   p.amax_a = amax_v; p.amax_b = amax_dm;
-  p.a_planes = v_planes ? 1 : 0;
-  VCG_CHECK_ARG(!v_planes || (wp.bm == 128 && q.K % 32 == 0), "vcg_conv_wgrad: pre-split V needs the split-operand tile");
+  p.a_planes = 1;                  // V comes pre-split (k_wino_in_planes)
+  VCG_CHECK_ARG(wp.bm == 128 && q.K % 32 == 0, "vcg_conv_wgrad: pre-split V needs the split-operand tile");
   p.a_bytes = (uint32_t)((size_t)T * q.K * 4); p.b_bytes = (uint32_t)((size_t)T * q.Cout * 4);
   p.nbatch = 16; p.a_bstride = (uint32_t)((size_t)T * q.K); p.b_bstride = (uint32_t)((size_t)T * q.Cout);
   p.ktiles_total = wp.total; p.sk_len = wp.len; p.sk_units = wp.ntr * wp.ntn * wp.total; p.sk_ntn = wp.ntn;
@@ -2708,12 +2654,9 @@ static ConvGeom swapped_geom(const ConvGeom& g) {
 static int launch_colsum(const ConvGeom& gorig, const float* dy, float* gbias, float* part, hipStream_t st) {
   int tc, cgroups, rows, nchunk;
   colsum_plan(gorig, tc, cgroups, rows, nchunk);
-  uint32_t* ctr = vcg_in_tail_enabled() ? vcg_tail_counters(cgroups) : nullptr;
-  hipLaunchKernelGGL(k_colsum_partial, dim3(cgroups, nchunk), dim3(256), 0, st, dy, part, gorig.M, gorig.Cout, rows, tc, ctr, gbias,
-                     gorig.cout_log);
-  if (!ctr)
-    hipLaunchKernelGGL(k_colsum_final, dim3((gorig.cout_log + 7) / 8), dim3(256), 0, st, (const float*)part, gbias,
-                       gorig.Cout, nchunk, gorig.cout_log);
+  hipLaunchKernelGGL(k_colsum_partial, dim3(cgroups, nchunk), dim3(256), 0, st, dy, part, gorig.M, gorig.Cout, rows, tc);
+  hipLaunchKernelGGL(k_colsum_final, dim3((gorig.cout_log + 7) / 8), dim3(256), 0, st, (const float*)part, gbias,
+                     gorig.Cout, nchunk, gorig.cout_log);
   VCG_LAUNCH_CHECK("vcg_conv_wgrad(bias)");
   return 0;
 }

@@ -1,16 +1,15 @@
-// Forward convolutions whose INPUT has at most 4 channels and whose output has 64: the 7x7 stem of the encoders
-// (/root/reference/Networks.py:158, CaSb(3, 64, 7): 9.9 GF and a 134 MB output per call at batch 8) and the first 4x4 / stride-2
-// layer of the discriminators (:244, CaSb(3, 64, 4, 2, 1, LeakyReLU, no norm)).
+// Forward convolution whose INPUT has at most 4 channels and whose output has 64: the first 4x4 / stride-2 layer of the
+// discriminators (/root/reference/Networks.py:244, CaSb(3, 64, 4, 2, 1, LeakyReLU, no norm)).  (The 7x7 stem of the encoders
+// (:158) was built on the same kernel, measured and left on the generic kernel: see vcg_thinin_fwd_ok below.)
 //
-// As an implicit GEMM these layers have K = KH * KW * 4 with only 16 bytes per tap and pixel: the generic kernel's gather is one
-// 16-byte load per (row, tap) — 49 of them per output pixel — and it ran at 69 TF (stem) / 22 TF (discriminator) with the matrix
-// pipe ~10 % busy (profiles/r03_step_shapes.txt).  Here a workgroup owns a 16 x 16 block of output pixels and stages the input
+// As an implicit GEMM this layer has K = KH * KW * 4 with only 16 bytes per tap and pixel: the generic kernel's gather is one
+// 16-byte load per (row, tap) and it ran at 22 TF with the matrix pipe ~10 % busy (profiles/r03_step_shapes.txt).  Here a workgroup owns a 16 x 16 block of output pixels and stages the input
 // patch under it ONCE, as two fp16 pieces of 4 channels per pixel (8 bytes per pixel and piece).  With K ordered (kh, kw, c) and kw
 // padded to 8, the 32-wide K block of a kernel row kh is 8 NEIGHBOURING pixels x 4 channels = 64 contiguous bytes of the patch
 // row: the im2col matrix never exists, an A fragment (8 consecutive k = 2 pixels) is two ds_read_b64 at pixel
 // (oy * S + kh) * SW + ox * S + 2 * chunk.  The whole weight matrix (64 x KH x 32, zero for kw >= KW) is split into LDS once
 // per workgroup from the fp32 Wf block of the pack.  256 x 64 tile, 4 waves of 64 x 64 (2 x 2 accumulators of 32 x 32, hh and
-// cross-term chains as everywhere), KH x 2 MFMA slices.  Epilogue: bias + activation, NHWC store, and — for the stem — the
+// cross-term chains as everywhere), KH x 2 MFMA slices.  Epilogue: bias + activation, NHWC store, and — when the caller wants them — the
 // InstanceNorm partial sums of the block in double (the slab kernels' layout: [N][blocks per image][Cout][2]).
 #include "vcg_common.h"
 
@@ -195,23 +194,15 @@ __global__ __launch_bounds__(256, 2) void k_conv_thinin(ThinInP p) {
 }
 
 // ------------------------------------------------------------------------------------------------------------- host side
-// VCG_THININ: 0 = the generic implicit-GEMM kernel for both layers, as in round 3; 1 (default) = the discriminators' first layer
-// only; 2 = the stem as well.  The stem variant is as accurate as the kernel it replaces (tests/test_gpu_fullsize.py holds both to
-// 2e-6 against float64) and 144 -> 110 us per call, but it rounds differently, and on the batch-1 GAN fixture that moved ONE
-// gradient tensor (G.encoder.model.5.conv1.weight, whose reference fp32-vs-fp64 error is unusually small: 6.1e-3) from under
-// to over its fixture-calibrated bound — 2.84e-2 against 4 x 6.1e-3 = 2.43e-2, the ReLU-flip floor of that step being ~3e-2 on
-// its neighbours.  Rather than widen the bound for 0.14 ms per step, the stem keeps the round-3 kernel by default.
-static int thinin_mode() {
-  static const int m = [] { const char* e = getenv("VCG_THININ"); return e ? atoi(e) : 1; }();
-  return m;
-}
+// The discriminators' first layer only.  A <7, 7, 1> instantiation for the encoders' stem was as accurate as the generic
+// implicit-GEMM kernel it would replace (both held to 2e-6 against float64) and 144 -> 110 us per call, but it rounds differently,
+// and on the batch-1 GAN fixture that moved ONE gradient tensor (G.encoder.model.5.conv1.weight, whose reference fp32-vs-fp64
+// error is unusually small: 6.1e-3) from under to over its fixture-calibrated bound — 2.84e-2 against 4 x 6.1e-3 = 2.43e-2, the
+// ReLU-flip floor of that step being ~3e-2 on its neighbours.  Rather than widen the bound for 0.14 ms per step,
+// the stem keeps the round-3 kernel.
 bool vcg_thinin_fwd_ok(const ConvGeom& g) {
-  const int mode = thinin_mode();
-  if (mode <= 0) return false;
-  const bool stem = g.KH == 7 && g.KW == 7 && g.stride == 1 && g.pad == 3 && mode >= 2;
-  const bool disc = g.KH == 4 && g.KW == 4 && g.stride == 2 && g.pad == 1;
-  return (stem || disc) && g.ups == 1 && g.Cin == 4 && g.Cout == 64 && g.Ho % 16 == 0 && g.Wo % 16 == 0 && g.Ho > 0 && g.Wo > 0 &&
-         (!g.reflect || (g.H > g.pad + 8 && g.W > g.pad + 8));
+  return g.KH == 4 && g.KW == 4 && g.stride == 2 && g.pad == 1 && g.ups == 1 && g.Cin == 4 && g.Cout == 64 && g.Ho % 16 == 0 &&
+         g.Wo % 16 == 0 && g.Ho > 0 && g.Wo > 0 && (!g.reflect || (g.H > g.pad + 8 && g.W > g.pad + 8));
 }
 int vcg_thinin_nchunk(const ConvGeom& g) { return (g.Ho / 16) * (g.Wo / 16); }
 int vcg_thinin_fwd(const ConvGeom& g, const float* x, const float* wf, const void* w_amax, const float* bias, float* y, double* in_part,
@@ -224,10 +215,7 @@ int vcg_thinin_fwd(const ConvGeom& g, const float* x, const float* wf, const voi
   p.pad = g.pad; p.reflect = g.reflect; p.act = g.act; p.nbx = g.Wo / 16; p.nby = g.Ho / 16;
   const dim3 grid((unsigned)(g.N * p.nbx * p.nby));
   const double flops = 2.0 * g.M * (double)g.K * g.Cout;
-  if (g.KH == 7) {
-    VcgProfScope prof("k_conv_thinin<7, 7, 1>", flops, st);
-    hipLaunchKernelGGL((k_conv_thinin<7, 7, 1>), grid, dim3(256), 0, st, p);
-  } else {
+  {
     VcgProfScope prof("k_conv_thinin<4, 4, 2>", flops, st);
     hipLaunchKernelGGL((k_conv_thinin<4, 4, 2>), grid, dim3(256), 0, st, p);
   }

@@ -11,37 +11,21 @@
 // Rounding: the transforms add a few ulp to the fp32 sums (measured in tests/test_gpu_parity.py against the
 // oracle at the same 1e-4 bound as the direct kernels).
 #include "vcg_common.h"
+#ifdef VCG_STAMP
 #include <stdlib.h>
+#endif
 
-int vcg_gemm_split_batched(const float* A, const void* BtPlanes, float* C, int rows, int K, int N, int batches, const VcgAmax& amax_a,
-                           const VcgAmax& amax_b, hipStream_t st, uint32_t* amax_a_keep = nullptr);
 // |G g G^T| <= (1.5)^2 max|g|: the transformed kernels are bounded by 4 x the kernel's largest magnitude
 #define WINO_U_SHIFT 2
 // |B^T d B| <= 4 max|d| (two +-1 pairs): the transformed input is bounded by 4 x the input's largest magnitude
 #define WINO_V_SHIFT 2
+// V is written pre-split (k_wino_in_planes), scaled by 4 x the input's amax, and the GEMMs (forward, data gradient, and the weight
+// gradient that re-reads a kept V) stage it with plain copies.
 int vcg_gemm_planes_batched(const void* APlanes, const void* BtPlanes, float* C, int rows, int K, int N, int batches, const VcgAmax& amax_a,
                             const VcgAmax& amax_b, hipStream_t st, uint32_t* amax_a_keep);
-// VCG_WINO_PLANES=0: V as fp32, split inside the GEMM (A/B measurements).  Default: k_wino_in writes V pre-split — the same bytes —
-// scaled by 4 x the input's amax, and the GEMMs (forward, data gradient, and the weight gradient that re-reads a kept V) stage it
-// with plain copies.
-// Gates of the three directions on Kc Cout / (Kc + Cout) (what the GEMMs save per float the transforms move); VCG_WINO_GATE_F / _D / _W
-// override them for A/B measurements (tools/conv_bench.py).  Round 3 (three fp16 MFMAs per product instead of six bf16 ones: the
-// direct kernels' matrix time halved, the transforms' traffic did not): re-measured per layer at batch 8 — forward D1 (85) 458 us
-// Winograd vs 360 direct, U2 (85) 109 vs 84, U1 / D2 (171) 79 / 267 vs 93 / 293: the forward gate moved from 64 to 100; data
-// gradient D1 476 vs 521, U2 118 vs 139: stays at 80; weight gradient D1 / U2 (85): the ring kernel as before
-// (profiles/r03_wino_gates.txt)
-static long long wino_gate_env(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
-long long vcg_wino_gate_fwd() { static const long long v = wino_gate_env("VCG_WINO_GATE_F", 100); return v; }
-long long vcg_wino_gate_dgrad() { static const long long v = wino_gate_env("VCG_WINO_GATE_D", 80); return v; }
-long long vcg_wino_gate_wgrad() { static const long long v = wino_gate_env("VCG_WINO_GATE_W", 128); return v; }
-static bool wino_planes_on() {
-  static const int on = [] { const char* e = getenv("VCG_WINO_PLANES"); return e ? atoi(e) : 1; }();
-  return on != 0;
-}
 
 struct WinoP {
   const float* x;
-  float* v;
   const float* m;
   const float* bias;
   float* y;
@@ -49,10 +33,10 @@ struct WinoP {
   int th, tw, T, Kc;
   int off;     // patch origin = 2 * tile - off: 1 (pad 1) forward, 2 for the data gradient over the padded domain
   FastDiv fd_k4, fd_tw, fd_thtw, fd_c4, fd_co4;
-  unsigned long long* amax_slot;   // k_wino_in / k_wino_dy: where the largest magnitude of what they write goes (vcg_common.h), or null
+  unsigned long long* amax_slot;   // k_wino_dy: where the largest magnitude of what it writes goes (vcg_common.h), or null
   uint32_t amax_gen;
-  // k_wino_in, planes mode (vplanes != null): V is written already split — fp16 planes [xi][t][Kc / 32][2][32] of V / s, the A
-  // operand of the GEMM as a pure copy — with s from the INPUT's amax: |B^T d B| <= 4 max|d|, so its scale is known before V is
+  // k_wino_in_planes / k_wino_in_tr: V is written already split — fp16 planes [xi][t][Kc / 32][2][32] of V / s, the A operand of
+  // the GEMM as a pure copy — with s from the INPUT's amax: |B^T d B| <= 4 max|d|, so its scale is known before V is
   VcgAmax amax_x;
   unsigned short* vplanes;
   // k_wino_in_planes / k_wino_in_tr, deferred InstanceNorm (vcg_conv_fwd_in_pre): x is the RAW output t of the previous conv and the
@@ -69,65 +53,8 @@ __device__ __forceinline__ float4 wino_pre_apply(const float4& v, const float4& 
 __device__ __forceinline__ float4 f4sub(const float4& a, const float4& b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float4 f4sum(const float4& a, const float4& b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
-// one thread: one tile x 4 consecutive k (same unshuffle phase (i, j), channels c..c+3)
-__global__ __launch_bounds__(256) void k_wino_in(WinoP p) {
-  __shared__ uint32_t amax_red[4];
-  uint32_t amax = 0;
-  const uint32_t k4n = (uint32_t)p.Kc / 4;
-  const size_t total = (size_t)p.T * k4n;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
-    const uint32_t t = (uint32_t)(idx / k4n);
-    const uint32_t k4 = (uint32_t)(idx - (size_t)t * k4n);
-    const uint32_t ph = fd_div(k4, p.fd_c4);                      // unshuffle phase i*2 + j (0 when ups == 1)
-    const int c = (int)(k4 - ph * (uint32_t)(p.Cin / 4)) * 4;
-    const int pi = (int)(ph >> 1), pj = (int)(ph & 1);
-    const uint32_t n = fd_div(t, p.fd_thtw);
-    const uint32_t rem = t - n * (uint32_t)(p.th * p.tw);
-    const uint32_t ty = fd_div(rem, p.fd_tw);
-    const int tx = (int)(rem - ty * (uint32_t)p.tw);
-    const float* xn = p.x + (size_t)n * p.H * p.W * p.Cin;
-    float4 d[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      int ih = 2 * (int)ty - p.off + r;
-      bool okh = true;
-      if (p.reflect) ih = reflect_idx(ih, p.Hl);
-      else okh = ih >= 0 && ih < p.Hl;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        int iw = 2 * tx - p.off + s;
-        bool ok = okh;
-        if (p.reflect) iw = reflect_idx(iw, p.Wl);
-        else ok = ok && iw >= 0 && iw < p.Wl;
-        d[r][s] = ok ? *reinterpret_cast<const float4*>(xn + ((size_t)(ih * p.ups + pi) * p.W + (iw * p.ups + pj)) * p.Cin + c)
-                     : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-    // B^T d: rows (d0 - d2, d1 + d2, d2 - d1, d1 - d3); then the same on the columns
-    float4 e[4][4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      e[0][s] = f4sub(d[0][s], d[2][s]);
-      e[1][s] = f4sum(d[1][s], d[2][s]);
-      e[2][s] = f4sub(d[2][s], d[1][s]);
-      e[3][s] = f4sub(d[1][s], d[3][s]);
-    }
-    float* vb = p.v + (size_t)t * p.Kc + (size_t)k4 * 4;
-    const size_t plane = (size_t)p.T * p.Kc;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const float4 o0 = f4sub(e[a][0], e[a][2]), o1 = f4sum(e[a][1], e[a][2]), o2 = f4sub(e[a][2], e[a][1]), o3 = f4sub(e[a][1], e[a][3]);
-      *reinterpret_cast<float4*>(vb + (size_t)(a * 4 + 0) * plane) = o0;
-      *reinterpret_cast<float4*>(vb + (size_t)(a * 4 + 1) * plane) = o1;
-      *reinterpret_cast<float4*>(vb + (size_t)(a * 4 + 2) * plane) = o2;
-      *reinterpret_cast<float4*>(vb + (size_t)(a * 4 + 3) * plane) = o3;
-      const uint32_t m01 = max(vcg_abs_bits4(o0), vcg_abs_bits4(o1)), m23 = max(vcg_abs_bits4(o2), vcg_abs_bits4(o3));
-      amax = max(amax, max(m01, m23));
-    }
-  }
-  if (p.amax_slot) vcg_amax_publish(amax, p.amax_slot, p.amax_gen, amax_red);     // uniform: the GEMM that reads V scales by it
-}
-// the same transform, V written as pre-split planes (WinoP::vplanes)
+// V = B^T d B as pre-split planes (WinoP::vplanes); one thread: one tile x 4 consecutive k (same unshuffle phase (i, j), channels
+// c..c+3).  B^T d: rows (d0 - d2, d1 + d2, d2 - d1, d1 - d3); then the same on the columns
 __global__ __launch_bounds__(256) void k_wino_in_planes(WinoP p) {
   float sc, inv;
   vcg_scale_of(vcg_amax_bits(p.amax_x), p.amax_x.shift, sc, inv);
@@ -247,7 +174,7 @@ __global__ __launch_bounds__(256) void k_wino_out(WinoP p) {
 // The same output transform for a layer whose output goes into an InstanceNorm: it also leaves the statistics' chunk
 // partials (sum and sum of squares per (image, channel), in double: norm.hip) so that no extra pass has to re-read y.
 // Grid (chunk of tiles, image, channel-quad group); thread = (channel quad, tile lane), as in k_in_partial.
-__global__ __launch_bounds__(256) void k_wino_out_stats(WinoP p, double* __restrict__ part, NormPlan pl, VcgInTail tail) {
+__global__ __launch_bounds__(256) void k_wino_out_stats(WinoP p, double* __restrict__ part, NormPlan pl) {
   __shared__ double r1[256 * 4];
   __shared__ double r2[256 * 4];
   const int tc = threadIdx.x % pl.TC, tp = threadIdx.x / pl.TC;
@@ -319,14 +246,9 @@ __global__ __launch_bounds__(256) void k_wino_out_stats(WinoP p, double* __restr
     double* o = part + (((size_t)n * pl.nchunk + blockIdx.x) * p.Cout + c4 * 4) * 2;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      vcg_store_sc1(o + 2 * e, s1[e]);
-      vcg_store_sc1(o + 2 * e + 1, s2[e]);
+      o[2 * e] = s1[e];
+      o[2 * e + 1] = s2[e];
     }
-  }
-  if (tail.out1) {                    // the last chunk block of this (image, channel group) writes mean / rstd (vcg_common.h)
-    __syncthreads();                  // r1 / r2 are free again
-    vcg_in_tail_run<0>(tail, part, n, blockIdx.z * pl.TC * 4, pl.TC * 4, p.Cout, pl.nchunk, tail.counters + n * pl.cgroups + blockIdx.z,
-                       (uint32_t)pl.nchunk, r1);
   }
 }
 
@@ -736,8 +658,8 @@ bool vcg_wino_fwd_ok(const ConvGeom& g) {
   const unsigned long long T = (unsigned long long)g.N * (g.Ho / 2) * (g.Wo / 2);
   const unsigned long long Kc = (unsigned long long)g.ups * g.ups * g.Cin;
   // the transforms move 16 T (Kc + Cout) floats each way while the GEMMs save ~ T Kc Cout multiplications: the forward
-  // pays from Kc Cout / (Kc + Cout) ~ 100 on (vcg_wino_gate_fwd above)
-  if (Kc * g.Cout < (unsigned long long)vcg_wino_gate_fwd() * (Kc + g.Cout)) return false;
+  // pays from Kc Cout / (Kc + Cout) ~ 100 on (kWinoGateFwd, vcg_common.h)
+  if (Kc * g.Cout < (unsigned long long)kWinoGateFwd * (Kc + g.Cout)) return false;
   return T * Kc * 4 < (1ull << 31) && T * g.Cout * 4 < (1ull << 31) && T * Kc * 16 < (1ull << 32);
 }
 // one transformed copy of the kernel as fp16 blocked planes: VCG_NP pieces x 2 bytes per value
@@ -758,7 +680,7 @@ int vcg_wino_weight(const ConvGeom& g, const float* w_oihw, float* u, const VcgA
 
 static WinoP wino_params(const ConvGeom& g) {
   WinoP p = {};
-  p.x = nullptr; p.v = nullptr; p.m = nullptr; p.bias = nullptr; p.y = nullptr;
+  p.x = nullptr; p.m = nullptr; p.bias = nullptr; p.y = nullptr;
   p.N = g.N; p.H = g.H; p.W = g.W; p.Cin = g.Cin; p.Cout = g.Cout; p.Hl = g.Hl; p.Wl = g.Wl; p.ups = g.ups;
   p.reflect = g.reflect; p.act = g.act; p.cout_log = g.cout_log;
   p.th = g.Ho / 2; p.tw = g.Wo / 2; p.T = g.N * p.th * p.tw; p.Kc = g.ups * g.ups * g.Cin;
@@ -779,24 +701,17 @@ bool vcg_wino_wgrad_ok(const ConvGeom& g) {
   // the transforms move 16 T (Kc + Cout) floats each way while the GEMMs save ~ T Kc Cout multiplications: it pays
   // from Kc Cout / (Kc + Cout) ~ 128 on (measured: 171 -> 1.46x, 85 -> 0.9x)
   const long long kc = (long long)g.ups * g.ups * g.Cin;
-  return vcg_wino_fwd_ok(g) && kc % 128 == 0 && kc * g.Cout >= vcg_wino_gate_wgrad() * (kc + g.Cout);
-}
-// VCG_WGRAD_TR=0: the stream-K reduction for every layer (A/B measurements)
-static bool wgrad_tr_on() {
-  static const int on = [] { const char* e = getenv("VCG_WGRAD_TR"); return e ? atoi(e) : 1; }();
-  return on != 0;
+  return vcg_wino_fwd_ok(g) && kc % 128 == 0 && kc * g.Cout >= kWinoGateWgrad * (kc + g.Cout);
 }
 // the weight gradient as a plain planes GEMM over transposed operands (k_wino_in_tr / k_wino_dy_tr above): enough output tiles
 // of 256 x 128 to fill the chip, whole 32-tile blocks.  Measured per layer at batch 8 (profiles/r03_wgrad_tr.txt; the forward pays
 // for the second, transposed copy of V): R weight gradient 154 -> 144 us but forward 81 -> 91; D3 226 -> 182 but 178 -> 223 (V is
-// 134 MB there); D4 319 -> 280 against 138 -> 155 — the one layer where it nets (VCG_WGRAD_TR=2: every layer that qualifies)
+// 134 MB there); D4 319 -> 280 against 138 -> 155 — per layer, the one where it nets.
+// Round 4: every qualifying layer (R, D3, D4) — re-measured on the round-4 build, same box, alternating runs: 36.28 / 36.07 ms per
+// step with D4 alone (round 3's choice: kc >= 2048 && T <= 1024) against 35.59 / 35.75 with all three (D4 alone: +1.4 %)
 bool vcg_wino_wgrad_tr_ok(const ConvGeom& g) {
-  if (!wgrad_tr_on() || !vcg_wino_wgrad_ok(g)) return false;
+  if (!vcg_wino_wgrad_ok(g)) return false;
   const long long kc = (long long)g.ups * g.ups * g.Cin, T = (long long)g.N * (g.Ho / 2) * (g.Wo / 2);
-  // round 4: every qualifying layer (R, D3, D4) by default — re-measured on the round-4 build, same box, alternating runs: 36.28 / 36.07
-  // ms per step with D4 alone (VCG_WGRAD_TR=1, round 3's default) against 35.59 / 35.75 with all three (+1.4 %)
-  static const int all = [] { const char* e = getenv("VCG_WGRAD_TR"); return !e || atoi(e) == 2; }();
-  if (!all && !(kc >= 2048 && T <= 1024)) return false;
   return T % 32 == 0 && kc % 32 == 0 && g.Cout % 128 == 0 && kc >= 256 && ((kc + 255) / 256) * (g.Cout / 128) * 16 >= 192 &&
          16 * kc * T * VCG_NP < (1ll << 32) && 16 * (long long)g.Cout * T * VCG_NP < (1ll << 32);
 }
@@ -837,35 +752,29 @@ int vcg_wino_wgrad(const ConvGeom& g, const float* x, const float* dy, float* gw
     if (vcg_gemm_planes_batched(Vt, dM, dU, p.Kc, p.T, g.Cout, 16, amax_v, amax_d, st, nullptr)) return -2;
     return vcg_wino_wgrad_reduce_one(g, dU, gw_oihw, st);
   }
-  p.x = x; p.v = V;
+  p.x = x;
   VcgAmax amax_v;
-  const bool planes = wino_planes_on();
   if (v_saved) {
-    // the forward's V: fp32 with its own amax behind it, or — planes mode — pre-split by 4 x the input's amax (the word behind it)
+    // the forward's V: pre-split by 4 x the input's amax (the word behind it)
     V = const_cast<float*>(v_saved);
-    amax_v = vcg_amax_stored(v_saved + wino_v_floats(g), planes ? WINO_V_SHIFT : 0);
-  } else if (planes) {
+    amax_v = vcg_amax_stored(v_saved + wino_v_floats(g), WINO_V_SHIFT);
+  } else {
     if (vcg_operand_amax(x, (size_t)g.N * g.H * g.W * g.Cin, x_handle, WINO_V_SHIFT, st, &amax_v)) return -2;
     p.amax_x = amax_v; p.vplanes = (unsigned short*)V;
     hipLaunchKernelGGL(k_wino_in_planes, dim3(wino_blocks((size_t)p.T * p.Kc / 4)), dim3(256), 0, st, p);
-  } else {
-    const VcgAmaxOut av = vcg_amax_new(st);
-    p.amax_slot = av.slot; p.amax_gen = av.gen;
-    hipLaunchKernelGGL(k_wino_in, dim3(wino_blocks((size_t)p.T * p.Kc / 4)), dim3(256), 0, st, p);
-    amax_v = vcg_amax_in(av);
   }
   const VcgAmaxOut ad = vcg_amax_new(st);
   p.amax_slot = ad.slot; p.amax_gen = ad.gen;
   hipLaunchKernelGGL(k_wino_dy, dim3(wino_blocks((size_t)p.T * g.Cout / 4)), dim3(256), 0, st, dy, dM, p);
   VCG_LAUNCH_CHECK("vcg_conv_wgrad(winograd transforms)");
-  return vcg_wino_wgrad_core(g, V, dM, p.T, gw_oihw, (char*)ws + tbytes, ws_bytes - tbytes, st, amax_v, vcg_amax_in(ad), planes);
+  return vcg_wino_wgrad_core(g, V, dM, p.T, gw_oihw, (char*)ws + tbytes, ws_bytes - tbytes, st, amax_v, vcg_amax_in(ad));
 }
 
 // data gradient over the padded domain (see k_wino_weight_dgrad)
 bool vcg_wino_dgrad_ok(const ConvGeom& g) {
   if (!wino_map_ok(g)) return false;               // its own gate below: the forward's (higher since round 3) says nothing about it
   const long long kc = (long long)g.ups * g.ups * g.Cin;
-  if (kc * g.Cout < vcg_wino_gate_dgrad() * (kc + g.Cout)) return false;             // measured: 85 -> 1.22..1.25x (D1, U2), 171 -> 1.3..1.5x
+  if (kc * g.Cout < kWinoGateDgrad * (kc + g.Cout)) return false;               // measured: 85 -> 1.22..1.25x (D1, U2), 171 -> 1.3..1.5x
   const unsigned long long Tp = (unsigned long long)g.N * (g.Ho / 2 + 1) * (g.Wo / 2 + 1);
   return Tp * kc * 4 < (1ull << 31) && Tp * g.Cout * 4 < (1ull << 31) && Tp * g.Cout * 16 < (1ull << 32);
 }
@@ -900,21 +809,13 @@ int vcg_wino_dgrad(const ConvGeom& g, const float* dy, const float* ud, const vo
   p.fd_co4 = make_fastdiv((uint32_t)kc / 4);
   float* V = (float*)ws;
   float* M = V + (((size_t)16 * p.T * g.Cout + 63) / 64) * 64;
-  p.v = V; p.m = M;
-  if (wino_planes_on()) {
-    VcgAmax ad;
-    if (vcg_operand_amax(dy, (size_t)g.N * g.Ho * g.Wo * g.Cout, dy_handle, WINO_V_SHIFT, st, &ad)) return -2;
-    p.amax_x = ad; p.vplanes = (unsigned short*)V;
-    hipLaunchKernelGGL(k_wino_in_planes, dim3(wino_blocks((size_t)p.T * g.Cout / 4)), dim3(256), 0, st, p);
-    VCG_LAUNCH_CHECK("vcg_conv_dgrad(winograd input transform)");
-    if (vcg_gemm_planes_batched(V, ud, M, p.T, g.Cout, kc, 16, ad, vcg_amax_stored(w_amax, WINO_U_SHIFT), st, nullptr)) return -2;
-  } else {
-    const VcgAmaxOut av = vcg_amax_new(st);
-    p.amax_slot = av.slot; p.amax_gen = av.gen;
-    hipLaunchKernelGGL(k_wino_in, dim3(wino_blocks((size_t)p.T * g.Cout / 4)), dim3(256), 0, st, p);
-    VCG_LAUNCH_CHECK("vcg_conv_dgrad(winograd input transform)");
-    if (vcg_gemm_split_batched(V, ud, M, p.T, g.Cout, kc, 16, vcg_amax_in(av), vcg_amax_stored(w_amax, WINO_U_SHIFT), st)) return -2;
-  }
+  p.m = M;
+  VcgAmax ad;
+  if (vcg_operand_amax(dy, (size_t)g.N * g.Ho * g.Wo * g.Cout, dy_handle, WINO_V_SHIFT, st, &ad)) return -2;
+  p.amax_x = ad; p.vplanes = (unsigned short*)V;
+  hipLaunchKernelGGL(k_wino_in_planes, dim3(wino_blocks((size_t)p.T * g.Cout / 4)), dim3(256), 0, st, p);
+  VCG_LAUNCH_CHECK("vcg_conv_dgrad(winograd input transform)");
+  if (vcg_gemm_planes_batched(V, ud, M, p.T, g.Cout, kc, 16, ad, vcg_amax_stored(w_amax, WINO_U_SHIFT), st, nullptr)) return -2;
   WinoP q = p;
   q.Kc = kc;                                      // the output side: k columns
   // output transform and fold in one pass: the padded image is never written
@@ -936,19 +837,17 @@ size_t vcg_wino_fwd_stats_doubles(const ConvGeom& g) {
 // fp16 pair keeps 22 bits for every element within 2^17 of the scale, so an element now needs to be within ~2^13 of the true
 // maximum to keep them all; smaller ones keep an absolute error of 2^-36 of the maximum, far under the fp32 rounding of any sum
 // they enter (the argument of vcg_common.h for the per-tensor scale).
-bool vcg_wino_pre_ok(const ConvGeom& g) { return vcg_wino_fwd_ok(g) && wino_planes_on(); }
 int vcg_wino_fwd(const ConvGeom& g, const float* x, const float* u, const void* w_amax, const float* bias, float* y, void* ws,
-                 size_t ws_bytes, hipStream_t st, double* in_part, const VcgInTail* tail_req, float* v_keep, uint64_t x_handle,
+                 size_t ws_bytes, hipStream_t st, double* in_part, const VcgInStatsOut* stats, float* v_keep, uint64_t x_handle,
                  const VcgPre* pre) {
   VCG_CHECK_ARG(ws && ws_bytes >= vcg_wino_fwd_workspace(g), "vcg_conv_fwd: workspace too small for the Winograd path (%zu)",
                 ws_bytes);
   WinoP p = wino_params(g);
   float* V = v_keep ? v_keep : (float*)ws;
   float* M = (float*)ws + (((size_t)16 * p.T * p.Kc + 63) / 64) * 64;
-  p.x = x; p.v = V; p.m = M; p.bias = bias; p.y = y;
+  p.x = x; p.m = M; p.bias = bias; p.y = y;
   uint32_t pre_bits = 0;
   if (pre && pre->mean) {
-    VCG_CHECK_ARG(wino_planes_on(), "vcg_conv_fwd_in_pre: needs the planes mode");
     p.pre_mean = pre->mean; p.pre_rstd = pre->rstd; p.pre_act = pre->act;
     const float bound = sqrtf((float)g.H * (float)g.W);
     memcpy(&pre_bits, &bound, 4);
@@ -957,16 +856,15 @@ int vcg_wino_fwd(const ConvGeom& g, const float* x, const float* u, const void* 
   if (v_keep && vcg_wino_wgrad_tr_ok(g)) {
     // this layer's weight gradient wants V TRANSPOSED (vcg_wino_wgrad): one transform kernel writes the forward's planes into
     // the workspace and the transposed ones into the caller's buffer
-    VCG_CHECK_ARG(wino_planes_on(), "VCG_WINO_PLANES=0 needs VCG_WGRAD_TR=0");
     VcgAmax ax;
     if (pre_bits) ax = vcg_amax_const(pre_bits, WINO_V_SHIFT);
     else if (vcg_operand_amax(x, (size_t)g.N * g.H * g.W * g.Cin, x_handle, WINO_V_SHIFT, st, &ax)) return -2;
     V = (float*)ws;
-    p.v = V; p.amax_x = ax; p.vplanes = (unsigned short*)V;
+    p.amax_x = ax; p.vplanes = (unsigned short*)V;
     hipLaunchKernelGGL(k_wino_in_tr, dim3(p.T / 32, p.Kc / 32), dim3(256), 0, st, p, (unsigned short*)v_keep);
     VCG_LAUNCH_CHECK("vcg_conv_fwd(winograd input transform, + transposed)");
     if (vcg_gemm_planes_batched(V, u, M, p.T, p.Kc, g.Cout, 16, ax, vcg_amax_stored(w_amax, WINO_U_SHIFT), st, keep_word)) return -2;
-  } else if (wino_planes_on()) {
+  } else {
     VcgAmax ax;
     if (pre_bits) ax = vcg_amax_const(pre_bits, WINO_V_SHIFT);
     else if (vcg_operand_amax(x, (size_t)g.N * g.H * g.W * g.Cin, x_handle, WINO_V_SHIFT, st, &ax)) return -2;
@@ -975,20 +873,13 @@ int vcg_wino_fwd(const ConvGeom& g, const float* x, const float* u, const void* 
     VCG_LAUNCH_CHECK("vcg_conv_fwd(winograd input transform)");
     // a kept V keeps the word it was scaled by behind it (vcg_wino_saved_floats): the weight gradient's GEMMs need the same scale
     if (vcg_gemm_planes_batched(V, u, M, p.T, p.Kc, g.Cout, 16, ax, vcg_amax_stored(w_amax, WINO_U_SHIFT), st, keep_word)) return -2;
-  } else {
-    const VcgAmaxOut av = vcg_amax_new(st);
-    p.amax_slot = av.slot; p.amax_gen = av.gen;
-    hipLaunchKernelGGL(k_wino_in, dim3(wino_blocks((size_t)p.T * p.Kc / 4)), dim3(256), 0, st, p);
-    VCG_LAUNCH_CHECK("vcg_conv_fwd(winograd input transform)");
-    if (vcg_gemm_split_batched(V, u, M, p.T, p.Kc, g.Cout, 16, vcg_amax_in(av), vcg_amax_stored(w_amax, WINO_U_SHIFT), st, keep_word)) return -2;
   }
   if (in_part) {
-    // statistics of y for the InstanceNorm that follows: chunk partials from this epilogue, combined by its last block
+    // statistics of y for the InstanceNorm that follows: chunk partials from this epilogue, combined by vcg_in_finalize
     const NormPlan pl = vcg_norm_plan(g.N, p.th * p.tw, g.Cout);
-    VcgInTail tail = vcg_in_tail_make(tail_req->out1, tail_req->out2, g.N * pl.cgroups, tail_req->HW, tail_req->eps);
-    hipLaunchKernelGGL(k_wino_out_stats, dim3(pl.nchunk, g.N, pl.cgroups), dim3(256), 0, st, p, in_part, pl, tail);
+    hipLaunchKernelGGL(k_wino_out_stats, dim3(pl.nchunk, g.N, pl.cgroups), dim3(256), 0, st, p, in_part, pl);
     VCG_LAUNCH_CHECK("vcg_conv_fwd(winograd output transform)");
-    return tail.out1 ? 0 : vcg_in_finalize(in_part, tail_req->out1, tail_req->out2, g.N, tail_req->HW, g.Cout, pl.nchunk, tail_req->eps, st);
+    return vcg_in_finalize(in_part, stats->mean, stats->rstd, g.N, stats->HW, g.Cout, pl.nchunk, stats->eps, st);
   } else {
     hipLaunchKernelGGL(k_wino_out, dim3(wino_blocks((size_t)p.T * g.Cout / 4)), dim3(256), 0, st, p);
   }

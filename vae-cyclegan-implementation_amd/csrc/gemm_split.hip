@@ -1,8 +1,8 @@
 // Batched dense GEMM for the Winograd layers on the 16-bit matrix pipe with fp32-level accuracy ("split-operand" arithmetic):
-//     C[z][m][n] = sum_k A[z][m][k] * Bt[z][n][k]      (A, C fp32 in memory; Bt pre-split planes; k contiguous in both)
+//     C[z][m][n] = sum_k A[z][m][k] * Bt[z][n][k]      (C fp32 in memory; A, Bt pre-split planes; k contiguous in both)
 //
 // gfx950 runs v_mfma_f32_32x32x16_{f16,bf16} at 16x the rate of v_mfma_f32_32x32x2_f32.  Rounds 1-2 split every fp32 operand
-// into three bf16 pieces and accumulated six products; measured from inside (tools/gemm_ws_probe.hip, round 3) those kernels
+// into three bf16 pieces and accumulated six products; measured from inside (round 3: profiles/r03_gemm_ws_probe.txt) those kernels
 // were not held back by their schedule but by the chip's answer to a dense MFMA stream — a lower clock — so the lever is
 // MFMAs per product.  Round 3: x / s = h + l as two fp16 pieces (22 mantissa bits), s a power of two from the tensor's largest
 // magnitude (vcg_common.h), and the THREE products hh, hl, lh — h*h in one fp32 accumulation chain, the two cross terms
@@ -12,14 +12,13 @@
 //
 // The B operand of every call site is a WEIGHT (the Winograd-transformed kernels U / Ud): it is split once per optimizer
 // step, when it is packed ("blocked planes": for Bt[n][k], K % 32 == 0,  bp[(n * K/32 + kb) * 64 + piece * 32 + j]  as fp16,
-// piece 0 / 1 = h / l of Bt[n][32 kb + j] / sB — 128 contiguous bytes per row and K block), so this kernel stages B with plain
-// 16-byte copies and only the activations (A) are scaled and split in the K loop.
+// piece 0 / 1 = h / l of Bt[n][32 kb + j] / sB — 128 contiguous bytes per row and K block).  The activations (A) are split into the
+// same layout by the kernel that produces them (the Winograd input transform), so both operands are staged with plain 16-byte copies.
 //
 // Tile 128 x BN (BN = 128 or 64), BK = 32, 256 threads = 2 x 2 waves, each wave (64 x BN/2) as 32x32 accumulators.
 // LDS images: per piece [rows][32] fp16, 64-byte rows, the four 16-byte chunks of a row XOR-swizzled by (row >> 2) & 3
 // so that the ds_read_b128 fragment reads (lane = row, 16 consecutive rows per LDS cycle) are conflict-free.
 #include "vcg_common.h"
-#include <stdlib.h>
 
 typedef unsigned int u32x4g __attribute__((ext_vector_type(4)));
 
@@ -35,17 +34,13 @@ struct GemmSplitP {
   uint32_t* amax_a_keep;              // where to leave A's amax bits for a later call that reads the same A (the kept V), or null
 };
 
-__device__ __forceinline__ float4 gs_bload4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  u32x4g v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
 #define GS_OOB 0x80000000u
 
-// APL: A comes pre-split too (k_wino_in_planes: fp16 planes [rows][K / 32][2][32] of A / sA) — both operands are staged with
+// A comes pre-split too (k_wino_in_planes: fp16 planes [rows][K / 32][2][32] of A / sA) — both operands are staged with
 // plain 16-byte copies and the K loop has no conversion arithmetic at all.
-template <int BN, bool APL = false>
+template <int BN>
 __global__ __launch_bounds__(256, 2) void k_gemm_split(GemmSplitP p) {
-  constexpr int BM = 128, NI = BN / 64, MI = 2, AR = BM / 32;
+  constexpr int BM = 128, NI = BN / 64, MI = 2;
   // [piece][row][32 fp16] as raw bytes: 64 B per row
   __shared__ __attribute__((aligned(16))) unsigned char As[VCG_NP][BM * 64];
   __shared__ __attribute__((aligned(16))) unsigned char Bs[VCG_NP][BN * 64];
@@ -71,17 +66,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_split(GemmSplitP p) {
     nt = (int)(l - (uint32_t)mt * gridDim.y);
   }
   const int m0 = mt * BM, n0 = nt * BN;
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-                                   APL ? (void*)((const unsigned short*)p.a + (size_t)zb * p.a_bstride) : (void*)(p.a + (size_t)zb * p.a_bstride), 0,
-                                   (int)p.a_bytes, 0x00020000),
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned short*)p.a + (size_t)zb * p.a_bstride), 0, (int)p.a_bytes, 0x00020000),
                                rb = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned short*)p.bt + (size_t)zb * p.b_bstride), 0, (int)p.b_bytes, 0x00020000);
-  const int s_row = tid >> 3, s_u = tid & 7;                    // staging: row (+32 i), k quad
-  uint32_t aoff[AR];
-#pragma unroll
-  for (int i = 0; i < AR; ++i) {
-    const int r = m0 + s_row + 32 * i;
-    aoff[i] = r < p.rows ? (uint32_t)(((size_t)r * p.K + s_u * 4) * 4) : GS_OOB;
-  }
   // B planes: thread (row b_r = tid >> 2, 16-byte chunk b_q = tid & 3 of a 64-byte piece row); pass j = (row half, piece)
   constexpr int BP = VCG_NP * BN / 64;                            // 16-byte copies per thread and K-step
   const int b_q = tid & 3, b_r = tid >> 2;
@@ -89,13 +75,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_split(GemmSplitP p) {
   const uint32_t boff0 = (uint32_t)(((size_t)(n0 + b_r) * KB) * VCG_PBYTES + b_q * 16);      // N % BN == 0: every row is in range
   const uint32_t bhalf = (uint32_t)KB * (64u * VCG_PBYTES);
   const uint32_t bsoff0 = (uint32_t)(b_r * 64 + ((b_q ^ ((b_r >> 2) & 3)) << 4));     // row + 64 keeps the swizzle term
-  // LDS byte offset of this thread's quad inside a piece image: row r, chunk (u >> 1) swizzled, half (u & 1)
-  uint32_t soff[AR];
-#pragma unroll
-  for (int i = 0; i < AR; ++i) {
-    const int r = s_row + 32 * i;
-    soff[i] = (uint32_t)(r * 64 + (((s_u >> 1) ^ ((r >> 2) & 3)) << 4) + ((s_u & 1) << 3));
-  }
 
   // acc: the h*h chain; lo: the two cross terms (<= 2^-11 of it).  One chain for all three would round the big running
   // sum three times per slice instead of once.
@@ -107,7 +86,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_split(GemmSplitP p) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = lo[i][j][e] = 0.f;
 
-  float4 va[AR];
   u32x4g vb[BP], vap[2 * VCG_NP];
   // A planes: the B pattern on the 128 rows of the M tile (rows past the matrix read as zeros)
   uint32_t apoff[2];
@@ -116,35 +94,19 @@ __global__ __launch_bounds__(256, 2) void k_gemm_split(GemmSplitP p) {
     const int r = m0 + b_r + 64 * h;
     apoff[h] = r < p.rows ? (uint32_t)(((size_t)r * KB) * VCG_PBYTES + b_q * 16) : GS_OOB;
   }
-  (void)vap; (void)apoff;
   const int nkt = KB;                                           // K % 32 == 0 (the planes' block size)
   auto load_tiles = [&](int kt) {
-    if constexpr (APL) {
 #pragma unroll
-      for (int j = 0; j < 2 * VCG_NP; ++j)
-        vap[j] = __builtin_amdgcn_raw_buffer_load_b128(
-            ra, (int)(apoff[j / VCG_NP] != GS_OOB ? apoff[j / VCG_NP] + (uint32_t)(j % VCG_NP) * 64u + (uint32_t)kt * VCG_PBYTES : GS_OOB), 0, 0);
-    } else {
-#pragma unroll
-      for (int i = 0; i < AR; ++i) va[i] = gs_bload4(ra, aoff[i] != GS_OOB ? aoff[i] + (uint32_t)kt * 128u : GS_OOB);
-    }
+    for (int j = 0; j < 2 * VCG_NP; ++j)
+      vap[j] = __builtin_amdgcn_raw_buffer_load_b128(
+          ra, (int)(apoff[j / VCG_NP] != GS_OOB ? apoff[j / VCG_NP] + (uint32_t)(j % VCG_NP) * 64u + (uint32_t)kt * VCG_PBYTES : GS_OOB), 0, 0);
 #pragma unroll
     for (int j = 0; j < BP; ++j)
       vb[j] = __builtin_amdgcn_raw_buffer_load_b128(rb, (int)(boff0 + (uint32_t)(j / VCG_NP) * bhalf + (uint32_t)(j % VCG_NP) * 64u + (uint32_t)kt * VCG_PBYTES), 0, 0);
   };
   auto store_tiles = [&]() {
-    if constexpr (APL) {
 #pragma unroll
-      for (int j = 0; j < 2 * VCG_NP; ++j) *reinterpret_cast<u32x4g*>(&As[j % VCG_NP][bsoff0 + 4096 * (j / VCG_NP)]) = vap[j];
-    } else {
-#pragma unroll
-      for (int i = 0; i < AR; ++i) {
-        uint2 h, l;
-        split4h(va[i], inv_a, h, l);
-        *reinterpret_cast<uint2*>(&As[0][soff[i]]) = h;
-        *reinterpret_cast<uint2*>(&As[1][soff[i]]) = l;
-      }
-    }
+    for (int j = 0; j < 2 * VCG_NP; ++j) *reinterpret_cast<u32x4g*>(&As[j % VCG_NP][bsoff0 + 4096 * (j / VCG_NP)]) = vap[j];
 #pragma unroll
     for (int j = 0; j < BP; ++j) *reinterpret_cast<u32x4g*>(&Bs[j % VCG_NP][bsoff0 + 4096 * (j / VCG_NP)]) = vb[j];
   };
@@ -257,24 +219,22 @@ int vcg_gd_set_stamp(void* buf) { return hipMemcpyToSymbol(HIP_SYMBOL(g_gd_stamp
 #define GD_T() 0ull
 #define GD_ACC(slot, t0) do { } while (0)
 #endif
-// SHAPE 32: v_mfma_f32_32x32x16_f16, a wave's 64 x 64 as 2 x 2 tiles x two 16-deep slices; SHAPE 16: v_mfma_f32_16x16x32_f16, 4 x 4
-// tiles x one 32-deep slice — the same fragment bytes, LDS reads, accumulator registers and matrix-pipe cycles, but the chip,
-// which answers an MFMA-dense loop with a lower clock (1.15-1.76 GHz here: profiles/r03_gemm_dma_stamps.txt), holds a higher one on
+// Matrix shape: v_mfma_f32_16x16x32_f16, a wave's 64 x 64 as 4 x 4 tiles x one 32-deep slice.  v_mfma_f32_32x32x16_f16 (2 x 2 tiles
+// x two 16-deep slices) has the same fragment bytes, LDS reads, accumulator registers and matrix-pipe cycles, but the chip, which
+// answers an MFMA-dense loop with a lower clock (1.15-1.76 GHz here: profiles/r03_gemm_dma_stamps.txt), holds a higher one on
 // the 16 x 16 shape (MI355X_MICROARCH.md, DVFS item 7)
-// STAG (SHAPE 16 only; round 4): the two waves that share a SIMD (wave w and w + 4 of the workgroup) run half a K-step apart.
+// Stagger (round 4): the two waves that share a SIMD (wave w and w + 4 of the workgroup) run half a K-step apart.
 // Measured from the instruction stream (profiles/r04_power_probe.txt has the clocks; the ISA: all 16 ds_read_b128 of a step are
 // issued right behind the barrier, by all 8 waves at once): a K-step was an LDS phase — 8 waves x 16 KB of fragments + 48 KB of
 // DMA writes at 128 B / clock: ~1 400 clocks with the matrix pipe idle — followed by a matrix phase (2 x 768 clocks per SIMD)
-// with the LDS idle.  With STAG the waves 4..7 keep the fragments of step kt in registers across the barrier and multiply them
+// with the LDS idle.  Staggered, the waves 4..7 keep the fragments of step kt in registers across the barrier and multiply them
 // in the FIRST half of interval kt + 1, while the waves 0..3 read theirs; in the second half the roles swap.  Same barriers, same
 // ring (stage kt is read in interval kt by both halves; the DMAs of interval kt overwrite the stage read in interval kt - 1), same
 // registers, same order of accumulation in every wave: bit-identical results.
-template <bool GD_SPREAD, int SHAPE, bool STAG = false>
 __global__ __launch_bounds__(512, 1) void k_gemm_planes_dma(GemmSplitP p) {
-  constexpr int MI = 2, NI = 2;
   __shared__ __attribute__((aligned(1024))) unsigned char smem[GD_STAGES * GD_STAGE];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wm = wid >> 1, wn = wid & 1, l31 = lane & 31, lh = lane >> 5;
+  const int wm = wid >> 1, wn = wid & 1;
   float sa_, inv_a, sb_, inv_b;
   {
     const uint32_t abits = vcg_amax_bits(p.amax_a);
@@ -326,30 +286,14 @@ __global__ __launch_bounds__(512, 1) void k_gemm_planes_dma(GemmSplitP p) {
     for (int q = 0; q < 6; ++q) issue_one(stage, kt, q);
   };
 
-  f32x16 acc[MI][NI], lo[MI][NI];
   f32x4 acc16[4][4], lo16[4][4];
-  if constexpr (SHAPE == 32) {
 #pragma unroll
-    for (int i = 0; i < MI; ++i)
+  for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < NI; ++j)
+    for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][j][e] = lo[i][j][e] = 0.f;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc16[i][j][e] = lo16[i][j][e] = 0.f;
-  }
-  uint32_t fa[MI], fb[NI];
-  int sa[MI], sb[NI];
-#pragma unroll
-  for (int i = 0; i < MI; ++i) { const int r = wm * 64 + i * 32 + l31; fa[i] = (uint32_t)(r * VCG_PBYTES); sa[i] = (r >> 1) & 7; }
-#pragma unroll
-  for (int j = 0; j < NI; ++j) { const int r = wn * 64 + j * 32 + l31; fb[j] = (uint32_t)(GD_A_BYTES + r * VCG_PBYTES); sb[j] = (r >> 1) & 7; }
-  // SHAPE 16: lane -> (row lane & 15 of a 16-row tile, 8-deep k slot lane >> 4)
+      for (int e = 0; e < 4; ++e) acc16[i][j][e] = lo16[i][j][e] = 0.f;
+  // lane -> (row lane & 15 of a 16-row tile, 8-deep k slot lane >> 4)
   const int r16 = lane & 15, kq = lane >> 4;
   uint32_t fa16[4], fb16[4];
   int sa16[4], sb16[4];
@@ -367,7 +311,7 @@ __global__ __launch_bounds__(512, 1) void k_gemm_planes_dma(GemmSplitP p) {
   if (nkt > 1) issue(1, 1);
   unsigned long long gd_t = GD_T();
   (void)gd_t;
-  // SHAPE 16 fragments live across the loop (STAG: the late half multiplies step kt - 1 while it is in iteration kt)
+  // the fragments live across the loop (the late half multiplies step kt - 1 while it is in iteration kt)
   f16x8 a16[VCG_NP][4], b16[VCG_NP][4];
   auto read16 = [&](int kt) {
     const unsigned char* st = smem + (kt % GD_STAGES) * GD_STAGE;
@@ -397,60 +341,22 @@ __global__ __launch_bounds__(512, 1) void k_gemm_planes_dma(GemmSplitP p) {
         c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[0][i], b16[1][j], c, 0, 0, 0);
         lo16[i][j] = c;
         acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[0][i], b16[0][j], acc16[i][j], 0, 0, 0);
-        if (GD_SPREAD && (j & 1) && q < 6) {                                   // after every second group: 8 slots for 6 DMAs
+        if ((j & 1) && q < 6) {                                                // after every second group: 8 slots for 6 DMAs
           __builtin_amdgcn_sched_barrier(0);
           if (more) issue_one(nstage, dkt, q);
           __builtin_amdgcn_sched_barrier(0);
           ++q;
         }
       }
-    if (!GD_SPREAD && more) issue(nstage, dkt);
   };
-  const bool late = STAG && wid >= 4;                                       // wave-uniform
+  const bool late = wid >= 4;                                               // wave-uniform
   for (int kt = 0; kt < nkt; ++kt) {
     if (kt + 1 < nkt) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");      // my six DMAs of stage kt have landed; stage kt + 1's stay in flight
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     GD_ACC(0, gd_t);
     gd_barrier();                                                           // everybody's have; everybody is done with stage kt - 1
     GD_ACC(1, gd_t);
-    if constexpr (SHAPE == 32) {
-      // The six DMAs of stage kt + 2 are issued ONE AT A TIME between the MFMA groups of this step, not in a burst behind the
-      // barrier (see mma16)
-      const bool more = kt + 2 < nkt;
-      const int nstage = (kt + 2) % GD_STAGES;
-      const unsigned char* st = smem + (kt % GD_STAGES) * GD_STAGE;
-      int q = 0;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        f16x8 a[VCG_NP][MI], b[VCG_NP][NI];
-#pragma unroll
-        for (int pc = 0; pc < VCG_NP; ++pc) {
-#pragma unroll
-          for (int i = 0; i < MI; ++i)
-            a[pc][i] = *reinterpret_cast<const f16x8*>(st + fa[i] + (((pc * 4 + 2 * s + lh) ^ sa[i]) << 4));
-#pragma unroll
-          for (int j = 0; j < NI; ++j)
-            b[pc][j] = *reinterpret_cast<const f16x8*>(st + fb[j] + (((pc * 4 + 2 * s + lh) ^ sb[j]) << 4));
-        }
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-          for (int j = 0; j < NI; ++j) {
-            f32x16 c = lo[i][j];
-            c = VCG_MFMA(a[1][i], b[0][j], c);
-            c = VCG_MFMA(a[0][i], b[1][j], c);
-            lo[i][j] = c;
-            acc[i][j] = VCG_MFMA(a[0][i], b[0][j], acc[i][j]);
-            if (GD_SPREAD && q < 6 && !(s == 1 && i == 1 && j == 1)) {          // after 7 of the 8 groups: 6 DMAs + one spare slot
-              __builtin_amdgcn_sched_barrier(0);
-              if (more) issue_one(nstage, kt + 2, q);
-              __builtin_amdgcn_sched_barrier(0);
-              ++q;
-            }
-          }
-      }
-      if (!GD_SPREAD && more) issue(nstage, kt + 2);
-    } else if (!late) {
+    if (!late) {
       read16(kt);
       mma16(kt + 2);
     } else {
@@ -463,42 +369,24 @@ __global__ __launch_bounds__(512, 1) void k_gemm_planes_dma(GemmSplitP p) {
     }
     GD_ACC(2, gd_t);
   }
-  if constexpr (SHAPE == 16) {
-    if (late) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      mma16(nkt);                                                            // the last step's products (no DMA left to issue)
-    }
+  if (late) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mma16(nkt);                                                              // the last step's products (no DMA left to issue)
   }
   float* const dst = p.c + (size_t)zb * p.c_bstride;
   const float os = sa_ * sb_;
-  if constexpr (SHAPE == 32) {
+  // 16 x 16 accumulator: lane -> column lane & 15, rows 4 (lane >> 4) + e
 #pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int n = n0 + wn * 64 + j * 32 + l31;
-      if (n >= p.N) continue;
+  for (int j = 0; j < 4; ++j) {
+    const int n = n0 + wn * 64 + j * 16 + r16;
+    if (n >= p.N) continue;
 #pragma unroll
-      for (int i = 0; i < MI; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int row = (e & 3) + 8 * (e >> 2) + 4 * lh;
-          const int m = m0 + wm * 64 + i * 32 + row;
-          if (m < p.rows) dst[(size_t)m * p.N + n] = (acc[i][j][e] + lo[i][j][e]) * os;
-        }
-    }
-  } else {
-    // 16 x 16 accumulator: lane -> column lane & 15, rows 4 (lane >> 4) + e
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = n0 + wn * 64 + j * 16 + r16;
-      if (n >= p.N) continue;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int m = m0 + wm * 64 + i * 16 + 4 * kq + e;
-          if (m < p.rows) dst[(size_t)m * p.N + n] = (acc16[i][j][e] + lo16[i][j][e]) * os;
-        }
-    }
+      for (int e = 0; e < 4; ++e) {
+        const int m = m0 + wm * 64 + i * 16 + 4 * kq + e;
+        if (m < p.rows) dst[(size_t)m * p.N + n] = (acc16[i][j][e] + lo16[i][j][e]) * os;
+      }
   }
 #ifdef VCG_GD_STAMP
   GD_ACC(3, gd_t);
@@ -509,12 +397,6 @@ __global__ __launch_bounds__(512, 1) void k_gemm_planes_dma(GemmSplitP p) {
   }
 #endif
 }
-// VCG_GEMM_DMA=0: the register-staged 128 x 128 kernel for every shape (A/B measurements)
-static bool gemm_dma_on() {
-  static const int on = [] { const char* e = getenv("VCG_GEMM_DMA"); return e ? atoi(e) : 1; }();
-  return on != 0;
-}
-
 // X[rows][K] fp32 -> blocked planes of X / s (see the top of this file), s from `amax`; one thread per 4 consecutive k.  K % 32 == 0.
 __global__ __launch_bounds__(256) void k_split_planes(const float* __restrict__ x, unsigned short* __restrict__ bp, size_t quads, int K, VcgAmax amax) {
   float s, inv;
@@ -554,56 +436,17 @@ int vcg_gemm_planes_batched(const void* APlanes, const void* BtPlanes, float* C,
   p.c_bstride = (size_t)rows * N;
   p.amax_a = amax_a; p.amax_b = amax_b; p.amax_a_keep = amax_a_keep;
   const int bn = (N % 128 == 0) ? 128 : 64;
-  if (bn == 128 && rows >= 256 && gemm_dma_on()) {
+  if (bn == 128 && rows >= 256) {
     dim3 grid((rows + GD_BM - 1) / GD_BM, N / GD_BN, batches);
     VcgProfScope prof("k_gemm_planes_dma", 2.0 * rows * (double)K * N * batches, st);
-    // VCG_GEMM_SPREAD=0: the DMAs of a stage in one burst behind the barrier (A/B measurements)
-    static const int spread = [] { const char* e = getenv("VCG_GEMM_SPREAD"); return e ? atoi(e) : 1; }();
-    // VCG_GEMM_SHAPE=32: v_mfma_f32_32x32x16_f16 tiles (A/B measurements)
-    static const int shape = [] { const char* e = getenv("VCG_GEMM_SHAPE"); return e ? atoi(e) : 16; }();
-    // VCG_GEMM_STAGGER=0: both waves of a SIMD in lockstep, as in round 3 (A/B measurements)
-    static const int stagger = [] { const char* e = getenv("VCG_GEMM_STAGGER"); return e ? atoi(e) : 1; }();
-    if (shape == 16 && stagger && spread) {
-      hipLaunchKernelGGL((k_gemm_planes_dma<true, 16, true>), grid, dim3(512), 0, st, p);
-    } else if (shape == 16) {
-      if (spread) hipLaunchKernelGGL((k_gemm_planes_dma<true, 16>), grid, dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((k_gemm_planes_dma<false, 16>), grid, dim3(512), 0, st, p);
-    } else {
-      if (spread) hipLaunchKernelGGL((k_gemm_planes_dma<true, 32>), grid, dim3(512), 0, st, p);
-      else hipLaunchKernelGGL((k_gemm_planes_dma<false, 32>), grid, dim3(512), 0, st, p);
-    }
+    hipLaunchKernelGGL(k_gemm_planes_dma, grid, dim3(512), 0, st, p);
     VCG_LAUNCH_CHECK("vcg_gemm_planes_batched(dma)");
     return 0;
   }
   dim3 grid((rows + 127) / 128, N / bn, batches);
   VcgProfScope prof(bn == 128 ? "k_gemm_split<128, planes>" : "k_gemm_split<64, planes>", 2.0 * rows * (double)K * N * batches, st);
-  if (bn == 128) hipLaunchKernelGGL((k_gemm_split<128, true>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((k_gemm_split<64, true>), grid, dim3(256), 0, st, p);
+  if (bn == 128) hipLaunchKernelGGL((k_gemm_split<128>), grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((k_gemm_split<64>), grid, dim3(256), 0, st, p);
   VCG_LAUNCH_CHECK("vcg_gemm_planes_batched");
-  return 0;
-}
-
-// rows x K (fp32) times (N x K)^T (blocked planes) per batch; K % 32 == 0, N % 64 == 0
-int vcg_gemm_split_batched(const float* A, const void* BtPlanes, float* C, int rows, int K, int N, int batches, const VcgAmax& amax_a,
-                           const VcgAmax& amax_b, hipStream_t st, uint32_t* amax_a_keep) {
-  const float* Bt = (const float*)BtPlanes;
-  VCG_CHECK_ARG(K % 32 == 0 && N % 64 == 0 && rows > 0, "vcg_gemm_split_batched: bad shape rows=%d K=%d N=%d", rows, K, N);
-  VCG_CHECK_ARG((unsigned long long)rows * K * 4 < (1ull << 31) && (unsigned long long)N * K * 2 * VCG_NP < (1ull << 31),
-                "vcg_gemm_split_batched: operand extents must stay below 2 GiB per batch");
-  VCG_CHECK_ARG((unsigned long long)rows * K * (unsigned long long)batches < (1ull << 32) &&
-                    (unsigned long long)N * K * VCG_NP * (unsigned long long)batches < (1ull << 32),
-                "vcg_gemm_split_batched: batch stride overflow");
-  GemmSplitP p;
-  p.a = A; p.bt = Bt; p.c = C; p.rows = rows; p.K = K; p.N = N;
-  p.a_bytes = (uint32_t)((size_t)rows * K * 4); p.b_bytes = (uint32_t)((size_t)N * K * 2 * VCG_NP);
-  p.a_bstride = (uint32_t)((size_t)rows * K); p.b_bstride = (uint32_t)((size_t)N * K * VCG_NP);
-  p.c_bstride = (size_t)rows * N;
-  p.amax_a = amax_a; p.amax_b = amax_b; p.amax_a_keep = amax_a_keep;
-  const int bn = (N % 128 == 0) ? 128 : 64;
-  dim3 grid((rows + 127) / 128, N / bn, batches);
-  VcgProfScope prof(bn == 128 ? "k_gemm_split<128>" : "k_gemm_split<64>", 2.0 * rows * (double)K * N * batches, st);
-  if (bn == 128) hipLaunchKernelGGL((k_gemm_split<128, false>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((k_gemm_split<64, false>), grid, dim3(256), 0, st, p);
-  VCG_LAUNCH_CHECK("vcg_gemm_split_batched");
   return 0;
 }

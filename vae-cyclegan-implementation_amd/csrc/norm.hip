@@ -10,18 +10,17 @@
 // order, so results are bitwise reproducible and free of the E[x^2]-E[x]^2 cancellation
 // a single fp32 pass would have.
 #include "vcg_common.h"
-#include <stdlib.h>
 
 static NormPlan make_plan(int N, int HW, int C) { return vcg_norm_plan(N, HW, C); }
 
 // ---- stage 1 of every per-(n,c) reduction -------------------------------------------
 // MODE 0: (sum t, sum t^2)
 // MODE 1: (sum g', sum g' * xhat)  with xhat=(t-mean)*rstd, g' = g * post_act'(xhat)
-template <int MODE, bool TAIL>
+template <int MODE>
 __global__ __launch_bounds__(256) void k_in_partial(const float* __restrict__ t, const float* __restrict__ g,
                                                     const float* __restrict__ mean, const float* __restrict__ rstd,
                                                     double* __restrict__ part, int H, int W, int C, NormPlan pl,
-                                                    int post_act, int shuffle, VcgInTail tail) {
+                                                    int post_act, int shuffle) {
   // fp64 accumulators: these sums cancel (var = E[x^2] - mean^2 for channels with |mean| >> std;
   // sum g' and sum g'*xhat in the backward), and torch's CPU kernel — the reference's numerics —
   // accumulates them in double too.  The kernel is HBM-bound, the extra fp64 adds are free.
@@ -95,20 +94,9 @@ __global__ __launch_bounds__(256) void k_in_partial(const float* __restrict__ t,
     double* o = part + (((size_t)n * pl.nchunk + blockIdx.x) * C + c4 * 4) * 2;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      if (TAIL) {
-        vcg_store_sc1(o + 2 * e, s1[e]);
-        vcg_store_sc1(o + 2 * e + 1, s2[e]);
-      } else {
-        o[2 * e] = s1[e];
-        o[2 * e + 1] = s2[e];
-      }
+      o[2 * e] = s1[e];
+      o[2 * e + 1] = s2[e];
     }
-  }
-  // the last of this (image, channel group)'s chunk blocks combines them (vcg_common.h; VCG_IN_TAIL=1)
-  if (TAIL) {
-    __syncthreads();                  // r1 / r2 are free again
-    vcg_in_tail_run<MODE>(tail, part, n, blockIdx.z * pl.TC * 4, pl.TC * 4, C, pl.nchunk, tail.counters + n * pl.cgroups + blockIdx.z,
-                          (uint32_t)pl.nchunk, r1);
   }
 }
 
@@ -192,55 +180,8 @@ __global__ __launch_bounds__(256) void k_in_apply(const float* __restrict__ t, c
   if (amax_slot) vcg_amax_publish(amax, amax_slot, amax_gen, amax_red);
 }
 
-// dt = epi'(t) * rstd * (g' - s1 - xhat * s2)
-__global__ __launch_bounds__(256) void k_in_bwd_apply(const float* __restrict__ g, const float* __restrict__ t,
-                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                      const float* __restrict__ s12, float* __restrict__ dt, int N,
-                                                      int H, int W, int C, int epi_act, int post_act, int shuffle,
-                                                      unsigned long long* amax_slot, uint32_t amax_gen) {
-  __shared__ uint32_t amax_red[4];
-  uint32_t amax = 0;
-  const int C4 = C / 4;
-  const size_t total = (size_t)N * H * W * C4;
-  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (size_t)gridDim.x * blockDim.x) {
-    const int c4 = (int)(idx % C4);
-    const size_t pixg = idx / C4;
-    const int n = (int)(pixg / ((size_t)H * W));
-    float4 v = *reinterpret_cast<const float4*>(t + pixg * C + c4 * 4);
-    float4 mu = *reinterpret_cast<const float4*>(mean + (size_t)n * C + c4 * 4);
-    float4 rs = *reinterpret_cast<const float4*>(rstd + (size_t)n * C + c4 * 4);
-    const float* sp = s12 + ((size_t)n * C + c4 * 4) * 2;
-    float4 gv;
-    if (shuffle) {
-      const int pix = (int)(pixg - (size_t)n * H * W);
-      const int h = pix / W, w = pix - h * W;
-      const float* gp = g + (((size_t)n * 2 * H + 2 * h) * (2 * W) + 2 * w) * C4 + c4;
-      gv.x = gp[0];
-      gv.y = gp[C4];
-      gv.z = gp[(size_t)2 * W * C4];
-      gv.w = gp[(size_t)2 * W * C4 + C4];
-    } else {
-      gv = *reinterpret_cast<const float4*>(g + pixg * C + c4 * 4);
-    }
-    float xh, gg;
-    float4 o;
-    xh = (v.x - mu.x) * rs.x; gg = gv.x * act_grad_from_in(xh, post_act);
-    o.x = act_grad_from_out(v.x, epi_act) * rs.x * (gg - sp[0] - xh * sp[1]);
-    xh = (v.y - mu.y) * rs.y; gg = gv.y * act_grad_from_in(xh, post_act);
-    o.y = act_grad_from_out(v.y, epi_act) * rs.y * (gg - sp[2] - xh * sp[3]);
-    xh = (v.z - mu.z) * rs.z; gg = gv.z * act_grad_from_in(xh, post_act);
-    o.z = act_grad_from_out(v.z, epi_act) * rs.z * (gg - sp[4] - xh * sp[5]);
-    xh = (v.w - mu.w) * rs.w; gg = gv.w * act_grad_from_in(xh, post_act);
-    o.w = act_grad_from_out(v.w, epi_act) * rs.w * (gg - sp[6] - xh * sp[7]);
-    *reinterpret_cast<float4*>(dt + pixg * C + c4 * 4) = o;
-    amax = max(amax, vcg_abs_bits4(o));
-  }
-  if (amax_slot) vcg_amax_publish(amax, amax_slot, amax_gen, amax_red);
-}
-
-// The same dt, by the workgroups of k_in_partial (one pixel chunk x TC channel quads of one image), which lets the kernel leave
-// the COLUMN SUMS of what it writes: the bias gradient of the conv in front of this InstanceNorm is sum over pixels of dt
+// dt = epi'(t) * rstd * (g' - s1 - xhat * s2), by the workgroups of k_in_partial (one pixel chunk x TC channel quads of one image),
+// which lets the kernel leave the COLUMN SUMS of what it writes: the bias gradient of the conv in front of this InstanceNorm is sum over pixels of dt
 // (conv -> ReLU -> IN blocks: D, U, R.conv1 — /root/reference/Networks.py:93-95), which used to be a pass of its own over dt
 // (k_colsum_partial: 64 launches and ~2 GB per CycleVAEGAN step).  colpart[(n * nchunk + chunk) * C + c], summed in a fixed
 // order by k_in_colsum_final.
@@ -377,15 +318,10 @@ int vcg_in_stats_pass(const float* t, float* mean, float* rstd, int N, int HW, i
   VCG_CHECK_ARG(ws_bytes >= vcg_in_workspace(N, HW, C), "vcg_in_stats: workspace too small");
   NormPlan pl = make_plan(N, HW, C);
   double* part = (double*)ws;
-  VcgInTail tail = vcg_in_tail_make(mean, rstd, N * pl.cgroups, HW, eps);
-  if (tail.out1)
-    hipLaunchKernelGGL((k_in_partial<0, true>), dim3(pl.nchunk, N, pl.cgroups), dim3(256), 0, st, t, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, part, HW, 1, C, pl, 0, 0, tail);
-  else
-    hipLaunchKernelGGL((k_in_partial<0, false>), dim3(pl.nchunk, N, pl.cgroups), dim3(256), 0, st, t, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, part, HW, 1, C, pl, 0, 0, tail);
+  hipLaunchKernelGGL(k_in_partial<0>, dim3(pl.nchunk, N, pl.cgroups), dim3(256), 0, st, t, (const float*)nullptr,
+                     (const float*)nullptr, (const float*)nullptr, part, HW, 1, C, pl, 0, 0);
   VCG_LAUNCH_CHECK("vcg_in_stats");
-  return tail.out1 ? 0 : vcg_in_finalize(part, mean, rstd, N, HW, C, pl.nchunk, eps, st);
+  return vcg_in_finalize(part, mean, rstd, N, HW, C, pl.nchunk, eps, st);
 }
 extern "C" int vcg_in_stats(const float* t, float* mean, float* rstd, int N, int HW, int C, float eps,
                             void* ws, size_t ws_bytes, void* stream) {
@@ -422,32 +358,19 @@ static int in_bwd_impl(const float* g, const float* t, const float* mean, const 
   float* s12 = (float*)(part + (size_t)N * pl.nchunk * C * 2);
   float* colpart = s12 + (size_t)N * C * 2 + 64;
   colpart = (float*)(((uintptr_t)colpart + 15) & ~(uintptr_t)15);
-  VcgInTail tail = vcg_in_tail_make(s12, nullptr, N * pl.cgroups, HW, 0.f);
-  if (tail.out1)
-    hipLaunchKernelGGL((k_in_partial<1, true>), dim3(pl.nchunk, N, pl.cgroups), dim3(256), 0, st, t, g, mean, rstd, part, H, W,
-                       C, pl, post_act, shuffle, tail);
-  else
-    hipLaunchKernelGGL((k_in_partial<1, false>), dim3(pl.nchunk, N, pl.cgroups), dim3(256), 0, st, t, g, mean, rstd, part, H, W,
-                       C, pl, post_act, shuffle, tail);
-  if (!tail.out1)
-    hipLaunchKernelGGL(k_in_final<1>, dim3((N * C + 31) / 32), dim3(256), 0, st, (const double*)part, s12,
-                       (float*)nullptr, N, HW, C, pl.nchunk, 0.f);
-  size_t total = (size_t)N * HW * (C / 4);
+  hipLaunchKernelGGL(k_in_partial<1>, dim3(pl.nchunk, N, pl.cgroups), dim3(256), 0, st, t, g, mean, rstd, part, H, W, C, pl, post_act,
+                     shuffle);
+  hipLaunchKernelGGL(k_in_final<1>, dim3((N * C + 31) / 32), dim3(256), 0, st, (const double*)part, s12,
+                     (float*)nullptr, N, HW, C, pl.nchunk, 0.f);
   const VcgAmaxOut ao = vcg_amax_new(st);
-  // VCG_IN_BWD_FLAT=1: the flat grid-stride kernel where no bias gradient is wanted, as before (A/B measurements).  Round 4: the
-  // (chunk, image, channel group) workgroups of the column-sum variant hold mean / rstd / s12 in registers and moved 4.97 TB/s
-  // where the flat kernel, which reloads them per element, moved 3.48 (profiles/r04_pmc_step_traffic.txt) — every layer takes them now
-  static const int flat = [] { const char* e = getenv("VCG_IN_BWD_FLAT"); return e ? atoi(e) : 0; }();
-  if (gbias || !flat) {
-    // dt (and, with gbias, its column sums: the bias gradient of the conv in front of this norm) in one pass
-    hipLaunchKernelGGL(k_in_bwd_apply_cs, dim3(pl.nchunk, N, pl.cgroups), dim3(256), 0, st, g, t, mean, rstd, (const float*)s12, dt,
-                       gbias ? colpart : (float*)nullptr, H, W, C, pl, epi_act, post_act, shuffle, ao.slot, ao.gen);
-    if (gbias)
-      hipLaunchKernelGGL(k_in_colsum_final, dim3((c_log + 7) / 8), dim3(256), 0, st, (const float*)colpart, gbias, C, N * pl.nchunk, c_log);
-  } else {
-    hipLaunchKernelGGL(k_in_bwd_apply, dim3(ew_blocks(total)), dim3(256), 0, st, g, t, mean, rstd, (const float*)s12,
-                       dt, N, H, W, C, epi_act, post_act, shuffle, ao.slot, ao.gen);
-  }
+  // dt (and, with gbias, its column sums: the bias gradient of the conv in front of this norm) in one pass.  Round 4: the (chunk,
+  // image, channel group) workgroups of this kernel hold mean / rstd / s12 in registers and moved 4.97 TB/s where a flat
+  // grid-stride kernel, which reloaded them per element, moved 3.48 (profiles/r04_pmc_step_traffic.txt) — every layer takes it,
+  // whether a bias gradient is wanted or not
+  hipLaunchKernelGGL(k_in_bwd_apply_cs, dim3(pl.nchunk, N, pl.cgroups), dim3(256), 0, st, g, t, mean, rstd, (const float*)s12, dt,
+                     gbias ? colpart : (float*)nullptr, H, W, C, pl, epi_act, post_act, shuffle, ao.slot, ao.gen);
+  if (gbias)
+    hipLaunchKernelGGL(k_in_colsum_final, dim3((c_log + 7) / 8), dim3(256), 0, st, (const float*)colpart, gbias, C, N * pl.nchunk, c_log);
   VCG_LAUNCH_CHECK("vcg_in_bwd");
   vcg_set_last_amax(vcg_amax_handle(ao));               // vcg_amax_last(): the largest magnitude of `dt`
   return 0;

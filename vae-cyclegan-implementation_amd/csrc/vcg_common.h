@@ -233,15 +233,12 @@ __host__ __device__ static inline void vcg_scale_of(uint32_t amax_bits, int shif
 struct NormPlan {
   int TC, TP, cgroups, nchunk, chunk;
 };
-bool vcg_in_tail_enabled();     // VCG_IN_TAIL=1: finalize in the producer (VcgInTail below); default 0 — measured slower, see there
 static inline NormPlan vcg_norm_plan(int N, int HW, int C) {
   NormPlan pl;
   int c4 = C / 4;
   int tc = 1;
-  // with VcgInTail on, at most 128 channels per workgroup: the workgroup that finalizes an (image, channel group) then has at
-  // least two chunk lanes per channel and a short chain of partials to walk
   // at most 128 channels per workgroup (rounds 1-2: up to 1024): more, narrower workgroups — measured on the step's InstanceNorm
-  // backward reductions 3.5 -> 3.3 ms per step — and what the finalizing workgroup of VcgInTail needs (>= 2 chunk lanes per channel)
+  // backward reductions 3.5 -> 3.3 ms per step
   while (tc * 2 <= c4 && tc * 2 <= 32) tc *= 2;
   pl.TC = tc;
   pl.TP = 256 / tc;
@@ -257,117 +254,19 @@ static inline NormPlan vcg_norm_plan(int N, int HW, int C) {
 }
 int vcg_in_finalize(const double* part, float* mean, float* rstd, int N, int HW, int C, int nchunk, float eps, hipStream_t st);
 
-// "Finalize in the producer" (round 3): the kernel that writes the chunk partials of an InstanceNorm reduction also combines
-// them.  Every workgroup that has written its chunk for (image n, channel range r) bumps counter [n * ranges + r]; the one
-// that arrives last — whichever it is — sums all `nchunk` partials of that range in the FIXED order k_in_final used to
-// (chunk lanes, then lanes in order: bitwise reproducible) and writes mean / rstd (MODE 0) or the two backward sums (MODE 1).
-// The separate 5-8 us finalize launch (134 per CycleVAEGAN step) and its dispatch gap are gone.  Counters come from a ring of
-// zero-initialised words in the code object; atomicInc wraps to zero on the last arrival, so a counter cleans itself.
-// MEASURED AND NOT ADOPTED (VERDICT r2 #5b; VCG_IN_TAIL=1 turns it on, every parity test passes with it): same box, 20 steps,
-// twice each: 38.61 / 38.33 ms per step with the tails, 37.83 / 37.90 with the separate finalize launches.  The finalize kernel
-// spreads N C / 32 blocks over the chip and is launch-latency bound (7 us); the last arriver walks nchunk x 128 channels of
-// write-through partials alone, at L2-miss latency, while the rest of the chip idles — longer than the launch it replaces.
-struct VcgInTail {
-  float* out1;            // mean (MODE 0) or s12 (MODE 1); null: no tail, the caller finalizes with vcg_in_finalize
-  float* out2;            // rstd (MODE 0)
-  uint32_t* counters;     // [N * ranges]
+// Where a conv that also emits the statistics of its output (vcg_conv_fwd_in) leaves them: the producer writes chunk partials,
+// and a separate vcg_in_finalize launch behind it combines them into mean / rstd.  ("Finalize in the producer" — the last
+// workgroup to arrive at a counter combines the partials inside the producing launch — was built in round 3, MEASURED AND NOT
+// ADOPTED: same box, 20 steps, twice each: 38.61 / 38.33 ms per step with it, 37.83 / 37.90 with the separate launches.  The
+// finalize kernel spreads N C / 32 blocks over the chip and is launch-latency bound (7 us); the last arriver walked nchunk x 128
+// channels of write-through partials alone, at L2-miss latency, while the rest of the chip idled.  DESIGN.md names the last
+// commit that has it.)
+struct VcgInStatsOut {
+  float* mean;            // [N][C]
+  float* rstd;            // [N][C]
   int HW;                 // pixels per image the partials cover
   float eps;
 };
-static inline VcgInTail vcg_in_tail_none() { VcgInTail t; t.out1 = nullptr; t.out2 = nullptr; t.counters = nullptr; t.HW = 0; t.eps = 0.f; return t; }
-uint32_t* vcg_tail_counters(int count);                 // `count` zero words nobody else is using (misc.hip)
-static inline VcgInTail vcg_in_tail_make(float* out1, float* out2, int ncounters, int HW, float eps) {
-  VcgInTail t = vcg_in_tail_none();
-  if (!vcg_in_tail_enabled()) return t;
-  t.counters = vcg_tail_counters(ncounters);
-  if (!t.counters) return t;
-  t.out1 = out1; t.out2 = out2; t.HW = HW; t.eps = eps;
-  return t;
-}
-#ifdef __HIPCC__
-// Visibility between workgroups inside one launch (cdna_hip_programming.md, Guideline 16): per-CU L1s are never refreshed by other
-// CUs' stores and the eight per-XCD L2s are not coherent with each other, so the partials are stored WRITE-THROUGH (sc1: relaxed
-// agent-scope atomic stores), every storing wave drains its stores, the block's barrier, ONE lane's relaxed agent-scope counter
-// add; the last arriver reads them back with sc1 loads.  No __threadfence(): an agent-scope release in every block writes the
-// XCD's whole L2 back (measured here: the step went from 38 to 59 ms).
-typedef __attribute__((address_space(1))) unsigned long long vcg_gu64;
-__device__ __forceinline__ void vcg_store_sc1(double* p, double v) {
-  __hip_atomic_store((vcg_gu64*)p, __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void vcg_store_sc1_f2(float* p, float x, float y) {              // p 8-byte aligned
-  const unsigned long long v = ((unsigned long long)__float_as_uint(y) << 32) | __float_as_uint(x);
-  __hip_atomic_store((vcg_gu64*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double vcg_load_sc1(const double* p) {
-  return __builtin_bit_cast(double, __hip_atomic_load((vcg_gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ float2 vcg_load_sc1_f2(const float* p) {
-  const unsigned long long v = __hip_atomic_load((vcg_gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return make_float2(__uint_as_float((uint32_t)v), __uint_as_float((uint32_t)(v >> 32)));
-}
-// all threads of the block, after their sc1 stores: true in the block that arrives last at `ctr` (of `expected`).
-// `flag`: one int of LDS that nothing else is using.
-__device__ __forceinline__ bool vcg_last_arrival(uint32_t* ctr, uint32_t expected, int* flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every storing wave: its write-through stores have landed
-  __syncthreads();
-  if (threadIdx.x == 0) *flag = atomicInc(ctr, expected - 1) == expected - 1;      // agent scope; wraps to zero on the last arrival
-  __syncthreads();
-  return *flag != 0;
-}
-// call with ALL threads of a 256-thread block, after the block's partials part[((n * nchunk + chunk) * C + c) * 2 + {0, 1}]
-// have been stored with vcg_store_sc1.  [c0, c0 + cn) = the channel range this block contributed to (cn a power of two), `ctr`
-// its counter, `expected` = blocks per (n, range) = nchunk.  sh: 512 doubles + one int of LDS free for the taking.
-template <int MODE>
-__device__ __forceinline__ void vcg_in_tail_run(const VcgInTail& t, const double* part, int n, int c0, int cn, int C, int nchunk,
-                                                uint32_t* ctr, uint32_t expected, double* sh) {
-  if (!vcg_last_arrival(ctr, expected, reinterpret_cast<int*>(sh + 512))) return;
-  const int cnl = cn < 256 ? cn : 256, L = 256 / cnl;
-  const int cl = threadIdx.x % cnl, lane = threadIdx.x / cnl;
-  for (int cb = 0; cb < cn; cb += cnl) {
-    const int c = c0 + cb + cl;
-    double a = 0.0, b = 0.0;
-    if (c < C) {
-      // four chunk loads in flight per thread (the loop is a chain of L2 round trips otherwise)
-      double a1 = 0.0, b1 = 0.0, a2 = 0.0, b2 = 0.0, a3 = 0.0, b3 = 0.0;
-      const double* q = part + ((size_t)n * nchunk * C + c) * 2;
-      const size_t ks = (size_t)C * 2;
-      int k = lane;
-      for (; k + 3 * L < nchunk; k += 4 * L) {
-        const double* q0 = q + (size_t)k * ks;
-        const double* q1 = q0 + (size_t)L * ks;
-        const double* q2 = q1 + (size_t)L * ks;
-        const double* q3 = q2 + (size_t)L * ks;
-        const double x0 = vcg_load_sc1(q0), y0 = vcg_load_sc1(q0 + 1), x1 = vcg_load_sc1(q1), y1 = vcg_load_sc1(q1 + 1);
-        const double x2 = vcg_load_sc1(q2), y2 = vcg_load_sc1(q2 + 1), x3 = vcg_load_sc1(q3), y3 = vcg_load_sc1(q3 + 1);
-        a += x0; b += y0; a1 += x1; b1 += y1; a2 += x2; b2 += y2; a3 += x3; b3 += y3;
-      }
-      for (; k < nchunk; k += L) { a += vcg_load_sc1(q + (size_t)k * ks); b += vcg_load_sc1(q + (size_t)k * ks + 1); }
-      a = (a + a1) + (a2 + a3);
-      b = (b + b1) + (b2 + b3);
-    }
-    if (L > 1) {
-      sh[threadIdx.x] = a;
-      sh[256 + threadIdx.x] = b;
-      __syncthreads();
-      if (lane == 0)
-        for (int k = 1; k < L; ++k) { a += sh[k * cnl + cl]; b += sh[256 + k * cnl + cl]; }
-    }
-    if (lane == 0 && c < C) {
-      const size_t idx = (size_t)n * C + c;
-      if (MODE == 0) {
-        const double m = a / t.HW;
-        double var = b / t.HW - m * m;
-        if (var < 0.0) var = 0.0;
-        t.out1[idx] = (float)m;
-        t.out2[idx] = (float)(1.0 / sqrt(var + (double)t.eps));
-      } else {
-        t.out1[idx * 2] = (float)(a / t.HW);
-        t.out1[idx * 2 + 1] = (float)(b / t.HW);
-      }
-    }
-  }
-}
-#endif
 int vcg_in_stats_pass(const float* t, float* mean, float* rstd, int N, int HW, int C, float eps, void* ws, size_t ws_bytes, hipStream_t st);
 
 // geometry derived from the int32[16] conv descriptor
@@ -386,7 +285,7 @@ int vcg_thin_fwd(const ConvGeom& g, const float* x, const float* wf, const float
 int vcg_thin_dgrad(const ConvGeom& g, const float* dy, const float* wf, float* dx, void* ws, size_t ws_bytes,
                    hipStream_t st);
 
-// conv_thinin.hip: forward of the layers with a 4-channel input and 64 outputs (the 7x7 stem, the discriminators' first layer)
+// conv_thinin.hip: forward of the 4x4 / stride-2 layer with a 4-channel input and 64 outputs (the discriminators' first layer)
 bool vcg_thinin_fwd_ok(const ConvGeom& g);
 int vcg_thinin_nchunk(const ConvGeom& g);
 int vcg_thinin_fwd(const ConvGeom& g, const float* x, const float* wf, const void* w_amax, const float* bias, float* y, double* in_part,
@@ -394,18 +293,20 @@ int vcg_thinin_fwd(const ConvGeom& g, const float* x, const float* wf, const voi
 
 // conv_wino.hip: Winograd F(2x2,3x3) forward for the 3x3 / stride-1 / pad-1 layers
 bool vcg_wino_weight_ok(const ConvGeom& g);
-long long vcg_wino_gate_fwd();
-long long vcg_wino_gate_dgrad();
-long long vcg_wino_gate_wgrad();
+// Gates of the three directions on Kc Cout / (Kc + Cout) (what the GEMMs save per float the transforms move).  Round 3 (three fp16
+// MFMAs per product instead of six bf16 ones: the direct kernels' matrix time halved, the transforms' traffic did not): re-measured
+// per layer at batch 8 — forward D1 (85) 458 us Winograd vs 360 direct, U2 (85) 109 vs 84, U1 / D2 (171) 79 / 267 vs 93 / 293: the
+// forward gate moved from 64 to 100; data gradient D1 476 vs 521, U2 118 vs 139: stays at 80; weight gradient D1 / U2 (85): the
+// ring kernel as before, 171 -> 1.46x (profiles/r03_wino_gates.txt)
+constexpr long long kWinoGateFwd = 100, kWinoGateDgrad = 80, kWinoGateWgrad = 128;
 bool vcg_wino_fwd_ok(const ConvGeom& g);
 size_t vcg_wino_weight_floats(const ConvGeom& g);
 size_t vcg_wino_fwd_workspace(const ConvGeom& g);
 int vcg_wino_weight(const ConvGeom& g, const float* w_oihw, float* u, const VcgAmax& amax_w, hipStream_t st);
 // deferred InstanceNorm of a conv's INPUT (vcg_conv_fwd_in_pre): mean / rstd [N][Cin] and the activation that follows the norm
 struct VcgPre { const float* mean; const float* rstd; int act; };
-bool vcg_wino_pre_ok(const ConvGeom& g);
 int vcg_wino_fwd(const ConvGeom& g, const float* x, const float* u, const void* w_amax, const float* bias, float* y, void* ws,
-                 size_t ws_bytes, hipStream_t st, double* in_part = nullptr, const VcgInTail* tail = nullptr, float* v_keep = nullptr,
+                 size_t ws_bytes, hipStream_t st, double* in_part = nullptr, const VcgInStatsOut* stats = nullptr, float* v_keep = nullptr,
                  uint64_t x_handle = 0, const VcgPre* pre = nullptr);
 size_t vcg_wino_saved_floats(const ConvGeom& g);
 size_t vcg_wino_fwd_stats_doubles(const ConvGeom& g);
@@ -418,7 +319,7 @@ bool vcg_wino_wgrad_tr_ok(const ConvGeom& g);
 int vcg_wino_wgrad_reduce_one(const ConvGeom& g, const float* dU, float* gw_oihw, hipStream_t st);   // dU [16][Kc][Cout], one part
 size_t vcg_wino_wgrad_core_workspace(const ConvGeom& g, int T);
 int vcg_wino_wgrad_core(const ConvGeom& g, const float* V, const float* dM, int T, float* gw_oihw, void* ws, size_t ws_bytes,
-                        hipStream_t st, const VcgAmax& amax_v, const VcgAmax& amax_dm, bool v_planes);
+                        hipStream_t st, const VcgAmax& amax_v, const VcgAmax& amax_dm);
 bool vcg_wino_dgrad_ok(const ConvGeom& g);
 size_t vcg_wino_dgrad_workspace(const ConvGeom& g);
 int vcg_wino_weight_dgrad(const ConvGeom& g, const float* w_oihw, float* ud, const VcgAmax& amax_w, hipStream_t st);
@@ -431,7 +332,7 @@ int vcg_slab_fwd_nchunk(const ConvGeom& g);
 bool vcg_slab_dgrad_ok(const ConvGeom& g);
 size_t vcg_slab_dgrad_workspace(const ConvGeom& g);
 int vcg_slab_fwd(const ConvGeom& g, const float* x, const void* wft_planes, size_t planes_bytes, const void* w_amax, const float* bias,
-                 float* y, double* in_part, const VcgInTail* tail, hipStream_t st, uint64_t x_handle = 0);
+                 float* y, double* in_part, const VcgInStatsOut* stats, hipStream_t st, uint64_t x_handle = 0);
 int vcg_slab_dgrad(const ConvGeom& g, const float* dy, const void* wfd_planes, size_t planes_bytes, const void* w_amax, float* dx,
                    void* ws, size_t ws_bytes, hipStream_t st, uint64_t dy_handle = 0);
 // conv_ring.hip: weight gradients of U4 / head / stem with row-ring staging (the taps are address offsets of the fragment reads)
