@@ -243,6 +243,22 @@ int vcg_kl_fwd(const float* mu, const float* lv, float* out, size_t n,
                void* ws, size_t ws_bytes, void* stream);
 int vcg_kl_bwd(const float* mu, const float* lv, const float* gout, float* gmu, float* glv,
                size_t n, void* stream);
+/* Structural loss (new: the reference trains on pixel-wise terms only): out[0] = 1 - mean SSIM(a, b) over the N images, the 3
+   logical channels and the (H - 10)(W - 10) valid positions of an 11 x 11 Gaussian window (sigma 1.5, normalised to sum 1,
+   C1 = 0.01^2, C2 = 0.03^2, population moments): vcg_image_metrics's definition without the clamp of either operand.  a
+   (generated), b (target): (N, H, W, 4) fp32, the networks' layout, 16-byte aligned, channel 3 never read into a sum; H, W >= 11
+   independent.  ws: vcg_ssim_loss_workspace(N, H, W) bytes = N ceil((H - 10) / 16) ceil((W - 10) / 16) doubles rounded up to 16
+   bytes (0 and vcg_last_error for bad sizes), 16-byte aligned: each tile's partial sum goes to a slot of its own and a final
+   pass sums the slots in a fixed order — no float atomics, the same input gives the same bits.  csrc/ssim_loss.hip. */
+size_t vcg_ssim_loss_workspace(int N, int H, int W);
+int vcg_ssim_loss_fwd(const float* a, const float* b, float* out, int N, int H, int W, void* ws, size_t ws_bytes,
+                      void* stream);
+/* ga = gout[0] * d loss / d a, (N, H, W, 4) with channel 3 = 0, written for every pixel; gout is read on the device.  With
+   B = dS/dvar_a, C = dS/dcov_ab, A = dS/dmu_a - 2 mu_a B - mu_b C per position and M = 3 N (H - 10)(W - 10):
+   ga(q) = -gout / M [ (w * A)(q) + 2 a(q) (w * B)(q) + b(q) (w * C)(q) ], * the transposed 11-tap filter over the valid
+   positions.  The coefficients are recomputed from a and b (a 20-pixel halo per 16 x 16 pixel tile): no workspace.  There is
+   no gradient with respect to b. */
+int vcg_ssim_loss_bwd(const float* a, const float* b, const float* gout, float* ga, int N, int H, int W, void* stream);
 /* out[0] = sum_i w[i]*(*s[i]) ; the composite loss lines Networks.py:941,2012-2018 */
 int vcg_lincomb_fwd(const float* const* s, const float* w, int count, float* out, void* stream);
 

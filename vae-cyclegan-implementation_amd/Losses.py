@@ -1,7 +1,7 @@
 """Atomic losses with the reference's class surface (Losses.py:14-121 of the reference),
 each reduction a HIP kernel (wavefront shuffle -> block partial -> ordered final sum).
 
-Only the six atomic classes exist here: the reference's composite loss classes
+Only the six atomic classes (and StructuralLoss, which the reference lacks) exist here: the reference's composite loss classes
 (Losses.py:123-379) are dead code there and are not part of the training step.
 """
 import torch.nn as nn
@@ -28,6 +28,14 @@ class IdentityLoss(nn.Module):
 
     def forward(self, x, y, Fx, Gy):
         return ops.weighted_sum([ops.l1_loss(Fx, x), ops.l1_loss(Gy, y)], [1.0, 1.0])
+
+
+class StructuralLoss(nn.Module):
+    """1 - mean SSIM(generated, target): 11 x 11 Gaussian window, the definition of the evaluator's SSIM metric without its
+    clamp (new: the reference has no structural term)."""
+
+    def forward(self, generated, target):
+        return ops.ssim_loss(generated, target)
 
 
 class GANLossGenerator(nn.Module):

@@ -18,7 +18,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .Losses import (CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss,
+from .Losses import (CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss, StructuralLoss,
                      KLDivergenceLoss, TranslationLoss)
 from .optim import FusedAdam
 
@@ -283,6 +283,15 @@ def _metrics_to_host(named, reducer=None):
     return dict(zip(keys, vec.tolist()))
 
 
+def _structural(kwargs):
+    """(lambda_ssim, StructuralLoss() or None) of a configure_loss call: with the weight at its default 0 no loss object exists and
+    the step computes, launches and reports exactly what it did before the term was added."""
+    lam = float(kwargs.get("lambda_ssim", 0.0))
+    if lam < 0.0:
+        raise ValueError(f"lambda_ssim must be >= 0, got {lam}")
+    return lam, (StructuralLoss() if lam > 0.0 else None)
+
+
 def _backward_and_step(loss, optimizer, reducer):
     """zero_grad -> backward -> [data-parallel gradient exchange, its buckets launched from inside the backward] -> step."""
     optimizer.zero_grad()
@@ -329,6 +338,8 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         self.optimizer = None
         self.grad_reducer = None
         self.loss_fn = None
+        self.loss_ssim_fn = None
+        self.lambda_ssim = 0.0
         self.apply(self._init_weights)
 
     def _init_weights(self, module):
@@ -344,6 +355,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
 
     def configure_loss(self, **kwargs):
         self.loss_fn = TranslationLoss()
+        self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
 
     def training_step(self, batch):
         if self.loss_fn is None:
@@ -353,7 +365,11 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         output = self(x)
         loss_trans = self.loss_fn(output, y)
-        value = float(loss_trans.detach())             # the reference's isnan/isinf guard syncs here too (:357)
+        G_loss, loss_ssim = loss_trans, None
+        if getattr(self, "loss_ssim_fn", None) is not None:     # (a caller's stand-in for `self` need not know the term)
+            loss_ssim = self.loss_ssim_fn(output, y)
+            G_loss = ops.weighted_sum([loss_trans, loss_ssim], [1.0, self.lambda_ssim])
+        value = float(G_loss.detach())                 # the reference's isnan/isinf guard syncs here too (:357)
         bad = math.isnan(value) or math.isinf(value)
         red = self.grad_reducer
         if red is not None:
@@ -363,8 +379,14 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         if bad:
             print("NaN or Inf detected in loss during training step; skipping the update.")
             self.optimizer.zero_grad()
-            return {"nan_detected": True, "G_loss": float("nan"), "loss_trans": float("nan"), "total_loss": float("nan")}
-        _backward_and_step(loss_trans, self.optimizer, red)
+            m = {"nan_detected": True, "G_loss": float("nan"), "loss_trans": float("nan"), "total_loss": float("nan")}
+            if loss_ssim is not None:
+                m["loss_ssim"] = float("nan")
+            return m
+        _backward_and_step(G_loss, self.optimizer, red)
+        if loss_ssim is not None:
+            m = _metrics_to_host({"G_loss": G_loss, "loss_trans": loss_trans, "loss_ssim": loss_ssim}, red)
+            return {"G_loss": m["G_loss"], "loss_trans": m["loss_trans"], "total_loss": m["G_loss"], "loss_ssim": m["loss_ssim"]}
         if red is not None:
             value = _metrics_to_host({"loss_trans": loss_trans}, red)["loss_trans"]      # the global-batch mean, as every other model logs
         return {"G_loss": value, "loss_trans": value, "total_loss": value}
@@ -375,6 +397,12 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         with torch.no_grad():
             x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
             output = self(x)
+            if self.loss_ssim_fn is not None:
+                loss_trans, loss_ssim = self.loss_fn(output, y), self.loss_ssim_fn(output, y)
+                m = _metrics_to_host({"G_loss": ops.weighted_sum([loss_trans, loss_ssim], [1.0, self.lambda_ssim]),
+                                      "loss_trans": loss_trans, "loss_ssim": loss_ssim})
+                return {"G_loss": m["G_loss"], "total_loss": m["G_loss"], "loss_trans": m["loss_trans"],
+                        "loss_ssim": m["loss_ssim"], "Gx": output}
             value = float(self.loss_fn(output, y))
             return {"G_loss": value, "total_loss": value, "loss_trans": value, "Gx": output}
 
@@ -392,7 +420,9 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self.grad_reducer = None
         self.loss_trans_fn = None
         self.loss_kl_fn = None
+        self.loss_ssim_fn = None
         self.lambda_kl = 0
+        self.lambda_ssim = 0.0
         self.apply(self._init_weights)
 
     def _init_weights(self, module):
@@ -412,6 +442,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self.loss_trans_fn = TranslationLoss()
         self.loss_kl_fn = KLDivergenceLoss()
         self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
+        self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
 
     def _check_configured(self):
         if self.optimizer is None:
@@ -426,20 +457,26 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         output, mu, logvar = self(x)
         loss_trans = self.loss_trans_fn(output, y)
         loss_kl = self.loss_kl_fn(mu, logvar)
-        G_loss = ops.weighted_sum([loss_trans, loss_kl], [1.0, self.lambda_kl])
-        return output, G_loss, loss_trans, loss_kl
+        named = {"G_loss": None, "loss_trans": loss_trans, "loss_kl": loss_kl}
+        terms, weights = [loss_trans, loss_kl], [1.0, self.lambda_kl]
+        if self.loss_ssim_fn is not None:
+            named["loss_ssim"] = self.loss_ssim_fn(output, y)
+            terms.append(named["loss_ssim"])
+            weights.append(self.lambda_ssim)
+        named["G_loss"] = ops.weighted_sum(terms, weights)
+        return output, named
 
     def training_step(self, batch):
         self._check_configured()
-        _, G_loss, loss_trans, loss_kl = self._losses(batch)
-        _backward_and_step(G_loss, self.optimizer, self.grad_reducer)
-        return _metrics_to_host({"G_loss": G_loss, "loss_trans": loss_trans, "loss_kl": loss_kl}, self.grad_reducer)
+        _, named = self._losses(batch)
+        _backward_and_step(named["G_loss"], self.optimizer, self.grad_reducer)
+        return _metrics_to_host(named, self.grad_reducer)
 
     def validation_step(self, batch):
         self._check_configured()
         with torch.no_grad():
-            output, G_loss, loss_trans, loss_kl = self._losses(batch)
-            m = _metrics_to_host({"G_loss": G_loss, "loss_trans": loss_trans, "loss_kl": loss_kl})
+            output, named = self._losses(batch)
+            m = _metrics_to_host(named)
             m["Gx"] = output
             return m
 
@@ -516,6 +553,8 @@ class CycleVAEGAN(nn.Module):
         self.loss_gan_disc = None
         self.loss_identity = None
         self.loss_kl = None
+        self.loss_ssim = None
+        self.lambda_ssim = 0.0
         # data-parallel hook: set by parallel.attach(); called as reducer(phase, optimizer)
         self.grad_reducer = None
 
@@ -570,6 +609,7 @@ class CycleVAEGAN(nn.Module):
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
         self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
+        self.lambda_ssim, self.loss_ssim = _structural(kwargs)
 
     def _check_configured(self, need_opt=True):
         if self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None or self.loss_kl is None:
@@ -648,6 +688,10 @@ class CycleVAEGAN(nn.Module):
             t["loss_identity"] = self.loss_identity(x, y, Fx, Gy)
             terms.append(t["loss_identity"])
             weights.append(self.lambda_identity)
+        if self.loss_ssim is not None:               # the structural cycle term; FGx and GFy are joined by now, as for loss_cycle
+            t["loss_ssim"] = ops.weighted_sum([self.loss_ssim(FGx, x), self.loss_ssim(GFy, y)], [1.0, 1.0])
+            terms.append(t["loss_ssim"])
+            weights.append(self.lambda_ssim)
         t["G_loss"] = ops.weighted_sum(terms, weights)
         # discriminator objective on the SAME discriminator outputs (reference :2038-2040)
         t["D_loss_x_real"], _ = ops.mse_const(DXx, 1.0)
@@ -667,6 +711,8 @@ class CycleVAEGAN(nn.Module):
         keys = list(self._METRIC_KEYS) + (list(self._MEAN_KEYS) if with_means else [])
         if self.paired:
             keys.append("loss_identity")
+        if self.loss_ssim is not None:
+            keys.append("loss_ssim")
         host = _metrics_to_host({k: t[k] for k in keys}, self.grad_reducer if with_means else None)
         out = {"total_loss": host["G_loss"] + host["D_loss"]}
         out.update(host)
@@ -742,6 +788,8 @@ class CycleAEGAN(CycleVAEGAN):
         self.loss_gan_gen = None
         self.loss_gan_disc = None
         self.loss_identity = None
+        self.loss_ssim = None
+        self.lambda_ssim = 0.0
         self.grad_reducer = None
 
     def forward(self, x, y):
@@ -763,6 +811,7 @@ class CycleAEGAN(CycleVAEGAN):
         self.lambda_gan = kwargs.get("lambda_gan", 1.0)
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
+        self.lambda_ssim, self.loss_ssim = _structural(kwargs)
 
     def _check_configured(self, need_opt=True):
         if self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None:
@@ -810,6 +859,10 @@ class CycleAEGAN(CycleVAEGAN):
             t["loss_identity"] = self.loss_identity(x, y, self.F(x), self.G(y))
             terms.append(t["loss_identity"])
             weights.append(self.lambda_identity)
+        if self.loss_ssim is not None:               # the structural cycle term; FGx and GFy are joined by now, as for loss_cycle
+            t["loss_ssim"] = ops.weighted_sum([self.loss_ssim(FGx, x), self.loss_ssim(GFy, y)], [1.0, 1.0])
+            terms.append(t["loss_ssim"])
+            weights.append(self.lambda_ssim)
         t["G_loss"] = ops.weighted_sum(terms, weights)
         t["D_loss_x_real"], _ = ops.mse_const(DXx, 1.0)
         t["D_loss_x_fake"], _ = ops.mse_const(DXFy, 0.0)

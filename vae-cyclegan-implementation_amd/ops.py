@@ -1074,6 +1074,48 @@ def l1_loss(a, b):
     return _L1Fn.apply(a, b)
 
 
+class _SsimLossFn(torch.autograd.Function):
+    """1 - mean SSIM(generated, target) (csrc/ssim_loss.hip); the gradient reaches `generated` only."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        lib = _native.lib()
+        if a.shape != b.shape:
+            raise RuntimeError(f"ssim_loss: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
+        if a.dim() != 4 or a.shape[1] != 3:
+            raise RuntimeError(f"ssim_loss: expected (N, 3, H, W) images, got shape {tuple(a.shape)}")
+        ap, bp = as_phys(a), as_phys(b)
+        n, h, w, _ = ap.shape
+        out = torch.empty((), dtype=torch.float32, device=a.device)
+        need = lib.vcg_ssim_loss_workspace(n, h, w)
+        if need == 0:
+            _native.check(-1, "vcg_ssim_loss_workspace")
+        ws = workspace(need, a.device)
+        _native.check(lib.vcg_ssim_loss_fwd(_ptr(ap), _ptr(bp), _ptr(out), n, h, w, _ptr(ws), ws.numel() * 4, _stream()),
+                      "vcg_ssim_loss_fwd")
+        ctx.save_for_backward(ap, bp)             # the backward recomputes its coefficients from the two images
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        lib = _native.lib()
+        ap, bp = ctx.saved_tensors
+        n, h, w, _ = ap.shape
+        g = g.contiguous()
+        ga = torch.empty_like(ap)
+        _native.check(lib.vcg_ssim_loss_bwd(_ptr(ap), _ptr(bp), _ptr(g), _ptr(ga), n, h, w, _stream()), "vcg_ssim_loss_bwd")
+        return logical_of(ga, 3), None
+
+
+def ssim_loss(generated, target):
+    """1 - mean SSIM over (N, 3, H, W) images, H, W >= 11: a 0-dim fp32 tensor.  `target` is an input image: no gradient."""
+    if target.requires_grad:
+        raise RuntimeError("ssim_loss: the target must not require a gradient (only d loss / d generated is computed)")
+    return _SsimLossFn.apply(generated, target)
+
+
 class _MseConstFn(torch.autograd.Function):
     """nn.MSELoss()(d, full_like(d, target)) and d.mean(); Losses.py:80-81,99-100, Networks.py:2048-2051."""
 

@@ -40,6 +40,7 @@ ALIASES = {"ae": "autoencoder", "vae_cyclegan": "cyclevaegan"}
 REFERENCE_ARCHS = ["autoencoder", "doubleae", "doublevae", "vae", "aegan", "vaegan", "cycleae", "cyclevae",
                    "cycleaegan", "cyclevaegan"]
 BUILT = tuple(REFERENCE_ARCHS)
+SSIM_ARCHS = ("autoencoder", "vae", "cycleaegan", "cyclevaegan")     # the models whose configure_loss takes lambda_ssim
 
 
 def create_model(architecture, paired=True, latent_dim=64):
@@ -203,6 +204,8 @@ def build_parser():
     p.add_argument("--lambda_identity", type=float, default=5.0)
     p.add_argument("--lambda_cycle", type=float, default=10.0)
     p.add_argument("--lambda_recon", type=float, default=1.0)
+    p.add_argument("--lambda_ssim", type=float, default=0.0,
+                   help="weight of the structural term 1 - SSIM beside the L1 (" + ", ".join(SSIM_ARCHS) + "); 0: not computed")
     p.add_argument("--output_dir", type=str, default="runs")
     p.add_argument("--save_freq", type=int, default=10)
     p.add_argument("--log_image_freq", type=int, default=5)
@@ -274,6 +277,9 @@ DATASET_MODALITY_DEFAULTS = {                        # reference train.py:367-37
 
 def main(args):
     args.architecture = ALIASES.get(args.architecture, args.architecture)
+    if getattr(args, "lambda_ssim", 0.0) != 0.0 and args.architecture not in SSIM_ARCHS:
+        raise ValueError(f"--lambda_ssim is supported by {', '.join(SSIM_ARCHS)} only, not by {args.architecture}: "
+                         "the flag would be ignored")
     # reference train.py:362-377, in its order: the autoencoder / VAE check sees the modalities as given, THEN the
     # per-dataset defaults fill in what was not given (they name the run directory and select hypersim's frames)
     if args.architecture in ("autoencoder", "vae"):
@@ -321,7 +327,8 @@ def main(args):
     model = create_model(args.architecture, paired=args.paired, latent_dim=args.latent_dim).to(device)
     model.configure_optimizers(lr=args.lr)
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
-                         lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon)
+                         lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
+                         lambda_ssim=getattr(args, "lambda_ssim", 0.0))
     if world > 1:
         parallel.attach(model)
     same_xy = args.architecture in ("autoencoder", "vae")
