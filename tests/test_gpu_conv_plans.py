@@ -2,10 +2,11 @@
 gemm_split.hip, conv_slab.hip, conv_ring.hip, conv_thin.hip, conv_thinin.hip), called through the C ABI and compared element by
 element with float64.
 
-conv_plan(cd) below mirrors the host-side dispatch in Python: which branch conv_fwd_impl, vcg_conv_dgrad and vcg_conv_wgrad_saved
-take for a descriptor, with the plan parameters that matter (tile, K slices, stream-K parts, reduction kernel, whether the forward
-leaves the InstanceNorm partials itself).  It mirrors the predicates and the cost models (gemm_plan, dgrad_setup, wgrad_plan,
-ring_plan, colsum_plan) — no kernel.  tests/test_native_abi.py checks it against the sizes the library reports without a GPU (they
+conv_plan(cd) below mirrors the host-side dispatch in Python: which branch plan_fwd, plan_dgrad and plan_wgrad (the one chain per
+direction that every size query and launch of conv_igemm.hip reads) choose for a descriptor, with the plan parameters that matter
+(tile, K slices, stream-K parts, reduction kernel, whether the forward leaves the InstanceNorm partials itself).  It mirrors the
+predicates and the cost models (gemm_plan, plan_dgrad's stride-2 re-plan, wgrad_plan, ring_plan, colsum_plan) and the layouts
+(pack_layout, the workspaces) — no kernel.  tests/test_native_abi.py checks it against the sizes the library reports without a GPU (they
 encode the K-slice, Winograd, slab, ring and thin choices) over the case list and a sweep of a few hundred geometries, and checks
 that CASES below still reach every branch of this table:
 
@@ -69,7 +70,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from test_gpu_norm_misc import Out, P, _st, _ws
+from test_gpu_norm_misc import Out, P, _st, _ws, norm_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -375,7 +376,7 @@ def conv_plan(cd):
     """The branch each direction takes for descriptor cd, with its plan parameters and the device kernel the profile table
     names for it (None: the branch launches no bracketed MFMA kernel of its own)."""
     g = geom(cd)
-    # ---------------------------------------------------------------- forward (conv_fwd_impl, conv_fwd_in_impl)
+    # ---------------------------------------------------------------- forward (plan_fwd)
     if thin_fold_ok(g):
         fwd = dict(branch="thin_fold", stats="pass", kernel="k_conv_slab<4, 1, 7, 1>" if slab_col_ok(g["KH"], g["Cin"]) else None)
     elif thin_fwd_ok(g):
@@ -398,7 +399,7 @@ def conv_plan(cd):
         fwd.update(bm=bm, bn=bn, nsplit=ns, kt_per=kt)
     fwd.setdefault("nsplit", 1)
     fwd["pre_ok"] = not thin_fold_ok(g) and not thin_fwd_ok(g) and wino_fwd_ok(g)
-    # ---------------------------------------------------------------- data gradient (vcg_conv_dgrad)
+    # ---------------------------------------------------------------- data gradient (plan_dgrad)
     s = g["stride"]
     if g["Hl"] % s or g["Wl"] % s:
         dg = dict(branch="unsupported", kernel=None)
@@ -429,7 +430,7 @@ def conv_plan(cd):
         dg = dict(branch=br, kernel=kern, bm=bm, bn=bn, nsplit=ns, kt_per=kt, replan=replan,
                   dbl_mirror=bool(g["reflect"] and (dbl(g["Hl"]) or dbl(g["Wl"]))))
     dg.setdefault("nsplit", 1)
-    # ---------------------------------------------------------------- weight gradient (vcg_conv_wgrad_saved)
+    # ---------------------------------------------------------------- weight gradient (plan_wgrad)
     if wino_wgrad_ok(g):
         T = wino_T(g)
         if wino_wgrad_tr_ok(g):
@@ -546,16 +547,42 @@ def saved_floats(g):
     return 16 * wino_T(g) * g["kc"] + 16 if wino_wgrad_ok(g) else 0
 
 
+def fwd_tile_stats(g):
+    """the direct split-operand forward leaves the partials itself: every 128-row tile inside one image, no K slices"""
+    if thin_fold_ok(g) or thin_fwd_ok(g) or thinin_fwd_ok(g) or wino_fwd_ok(g) or fwd_slab_ok(g):
+        return False
+    bm, bn, ns, _ = fwd_plan(g)
+    return bm == 128 and bn >= 64 and ns == 1 and wft_wanted(g) and (g["Ho"] * g["Wo"]) % 128 == 0
+
+
+def fwd_in_workspace(g):
+    """vcg_conv_fwd_in_workspace: the conv workspace rounded up to 256 bytes, then the InstanceNorm partials of whoever leaves them
+    (16 bytes per (image, chunk, channel): a double sum and a double sum of squares) or the workspace of the separate pass"""
+    N, HoWo, co = g["N"], g["Ho"] * g["Wo"], g["Cout"]
+    if not thin_fold_ok(g) and not thin_fwd_ok(g) and thinin_fwd_ok(g):
+        part = N * (g["Ho"] // 16) * (g["Wo"] // 16) * co * 16
+    elif wino_fwd_ok(g):
+        part = N * norm_plan(N, (g["Ho"] // 2) * (g["Wo"] // 2), co)["nchunk"] * co * 16
+    elif fwd_slab_ok(g) and g["Ho"] % 8 == 0 and g["Wo"] % 16 == 0:
+        part = N * (g["Ho"] // 8) * (g["Wo"] // 16) * co * 16
+    elif fwd_tile_stats(g):
+        part = N * (HoWo // 128) * co * 16
+    else:
+        part = N * norm_plan(N, HoWo, co)["nchunk"] * co * 20 + N * co * 8 + 512          # vcg_in_workspace
+    return _cdiv(fwd_workspace(g), 256) * 256 + part
+
+
 def library_sizes(lib, cd):
-    return dict(fwd_ws=lib.vcg_conv_fwd_workspace(cd), dgrad_ws=lib.vcg_conv_dgrad_workspace(cd),
+    return dict(fwd_ws=lib.vcg_conv_fwd_workspace(cd), fwd_in_ws=lib.vcg_conv_fwd_in_workspace(cd),
+                dgrad_ws=lib.vcg_conv_dgrad_workspace(cd),
                 wgrad_ws=lib.vcg_conv_wgrad_workspace(cd), pack=lib.vcg_pack_weight_floats(cd), reads_wf=lib.vcg_conv_reads_wf(cd),
                 saved=lib.vcg_conv_saved_floats(cd), pre_ok=lib.vcg_conv_pre_ok(cd))
 
 
 def mirror_sizes(cd):
     g = geom(cd)
-    return dict(fwd_ws=fwd_workspace(g), dgrad_ws=dgrad_workspace(g), wgrad_ws=wgrad_workspace(g), pack=pack_weight_floats(g),
-                reads_wf=reads_wf(g), saved=saved_floats(g), pre_ok=int(conv_plan(cd)["fwd"]["pre_ok"]))
+    return dict(fwd_ws=fwd_workspace(g), fwd_in_ws=fwd_in_workspace(g), dgrad_ws=dgrad_workspace(g), wgrad_ws=wgrad_workspace(g),
+                pack=pack_weight_floats(g), reads_wf=reads_wf(g), saved=saved_floats(g), pre_ok=int(conv_plan(cd)["fwd"]["pre_ok"]))
 
 
 def desc(n, h, w, cin, cout, k, stride=1, pad=1, reflect=1, ups=1, act=0, cin_log=None, cout_log=None):

@@ -198,9 +198,10 @@ def _plan_sweep():
 
 def test_conv_plan_mirror_matches_the_library_and_cases_hit_every_branch(pkg):
     """tests/test_gpu_conv_plans.py mirrors the convolution dispatch (conv_plan).  Without a GPU the library reports the sizes its
-    planners derive — forward / data / weight gradient workspaces, packed-weight floats, whether Wf is read, saved floats, whether
-    the normalising gather exists — which encode the K-slice, Winograd, slab, ring, thin and swapped choices: the mirror must
-    give the same numbers for the GPU case list and a sweep of 400 geometries.  And the case list must keep reaching every branch
+    planners (plan_fwd, plan_dgrad, plan_wgrad, pack_layout) derive — forward, forward-with-statistics, data and weight gradient
+    workspaces, packed-weight floats, whether Wf is read, saved floats, whether the normalising gather exists — which encode the
+    K-slice, Winograd, slab, ring, thin and swapped choices: the mirror must give the same numbers for the GPU case list and a
+    sweep of 400 geometries.  And the case list must keep reaching every branch
     of the module's table: a plan change that turns an edge case into an easy one fails here, naming the branch."""
     from test_gpu_conv_plans import CASES, REQUIRED, branch_labels, case_desc, library_sizes, mirror_sizes
     lib = pkg._native.lib()

@@ -1985,12 +1985,22 @@ static void fill_params(const ConvGeom& g, ConvP& p) {
   p.a_planes = 0;
 }
 
+static size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+
+// the extents of a / b for the bounds-checked buffer loads; `msg` is the caller's own wording of the limit
+static int set_extents(ConvP& p, unsigned long long ab, unsigned long long bb, const char* msg) {
+  VCG_CHECK_ARG(ab < (1ull << 31) && bb < (1ull << 31), "%s", msg);
+  p.a_bytes = (uint32_t)ab; p.b_bytes = (uint32_t)bb;
+  return 0;
+}
+
 // Tile and K-slice choice.  The 256 CUs want >= 512 workgroups.  If the largest tile that reaches that
 // exists, use it.  Otherwise (deep layers: M = N*16*16 pixels, K up to 18 432) keep the big, efficient
 // tile and slice K across blockIdx.z instead of shrinking the tile: partial tiles go to fp32 slabs that
 // k_splitk_finish sums in a fixed order (+ bias + activation).
-static void gemm_plan(long long rows, long long cols, int nkt, bool allow_split, int& bm, int& bn, int& nsplit,
-                      int& kt_per, int batches = 1, bool allow_bn32 = false, bool single_level = false) {
+struct Tile { int bm, bn, nsplit, kt_per; };
+static Tile gemm_plan(long long rows, long long cols, int nkt, bool allow_split, int batches = 1, bool allow_bn32 = false,
+                      bool single_level = false) {
   // cost model (us): rounds of resident workgroups x K-steps per workgroup x time per K-step of that tile,
   // plus the slab write+read of a K-sliced launch.  Same constants as wgrad_plan.
   struct Cand { int bm, bn, resident; double t_step; };
@@ -1998,7 +2008,7 @@ static void gemm_plan(long long rows, long long cols, int nkt, bool allow_split,
   const Cand cands[5] = {{128, 128, single_level ? 3 : 2, single_level ? 5.4 : 5.1}, {128, 64, 3, 4.7}, {64, 128, 3, 4.7},
                          {64, 64, 4, 4.8}, {128, 32, 4, 3.6}};
   double best = 1e30;
-  bm = 64; bn = 64; nsplit = 1; kt_per = nkt;
+  Tile out = {64, 64, 1, nkt};
   for (int ci = 0; ci < 5; ++ci) {
     const Cand& c = cands[ci];
     if (c.bn == 32 && !(allow_bn32 && cols <= 32)) continue;
@@ -2014,59 +2024,23 @@ static void gemm_plan(long long rows, long long cols, int nkt, bool allow_split,
       long long rounds = (tiles * real_ns + slots - 1) / slots;
       double t = rounds * kt * c.t_step;
       if (real_ns > 1) t += (double)real_ns * rows * cols * 8.0 / 3.0e6 + 3.0;   // + one more launch
-      if (t < best * 0.97) { best = t; bm = c.bm; bn = c.bn; nsplit = real_ns; kt_per = kt; }
+      if (t < best * 0.97) { best = t; out = {c.bm, c.bn, real_ns, kt}; }
     }
   }
+  return out;
 }
 
-#define DISPATCH_DGRAD(bm, bn, grid, stream, p)                                               \
-  do {                                                                                        \
-    if (bn == 32) hipLaunchKernelGGL((k_conv_dgrad<128, 32, 1>), grid, dim3(256), 0, stream, p); \
-    else DISPATCH_TILE(k_conv_dgrad, bm, bn, grid, stream, p);                                 \
-  } while (0)
-#define DISPATCH_FWD(bm, bn, grid, stream, p)                                                 \
-  do {                                                                                        \
-    if (bn == 32) hipLaunchKernelGGL((k_conv_fwd<128, 32, 1>), grid, dim3(256), 0, stream, p); \
-    else DISPATCH_TILE(k_conv_fwd, bm, bn, grid, stream, p);                                   \
-  } while (0)
-#define DISPATCH_TILE(KERNEL, bm, bn, grid, stream, p)                                        \
-  do {                                                                                        \
-    if (bm == 128 && bn == 128) hipLaunchKernelGGL((KERNEL<128, 128>), grid, dim3(256), 0, stream, p); \
-    else if (bm == 128 && bn == 64) hipLaunchKernelGGL((KERNEL<128, 64>), grid, dim3(256), 0, stream, p); \
-    else if (bm == 64 && bn == 128) hipLaunchKernelGGL((KERNEL<64, 128>), grid, dim3(256), 0, stream, p); \
-    else hipLaunchKernelGGL((KERNEL<64, 64>), grid, dim3(256), 0, stream, p);                  \
-  } while (0)
-
-// C[z][m][n] = sum_k A[z][m][k] * B[z][k][n]   (row-major, k and n multiples of 4) — the forward kernel run as a
-// 1x1 convolution over `rows` pixels, one batch per blockIdx.z.  Used by the Winograd path (conv_wino.hip).
-int vcg_gemm_batched(const float* A, const float* B, float* C, int rows, int K, int Ncols, int batches, hipStream_t st) {
-  ConvGeom g = {};
-  g.N = 1; g.H = 1; g.W = rows; g.Cin = K; g.Cout = Ncols; g.KH = g.KW = 1; g.stride = 1; g.pad = 0; g.reflect = 0;
-  g.ups = 1; g.act = VCG_ACT_NONE; g.cin_log = K; g.cout_log = Ncols;
-  g.Hl = 1; g.Wl = rows; g.Ho = 1; g.Wo = rows; g.M = rows; g.K = K; g.taps = 1;
-  ConvP p; fill_params(g, p);
-  p.a = A; p.b = B; p.bias = nullptr; p.out = C;
-  VCG_CHECK_ARG((unsigned long long)rows * K * 4 < (1ull << 31) && (unsigned long long)K * Ncols * 4 < (1ull << 31),
-                "vcg_gemm_batched: operand extents must stay below 2 GiB per batch");
-  p.a_bytes = (uint32_t)((size_t)rows * K * 4); p.b_bytes = (uint32_t)((size_t)K * Ncols * 4);
-  p.nbatch = batches; p.a_bstride = (uint32_t)((size_t)rows * K); p.b_bstride = (uint32_t)((size_t)K * Ncols);
-  p.out_bstride = (size_t)rows * Ncols;
-  VCG_CHECK_ARG((unsigned long long)rows * K * (unsigned long long)batches < (1ull << 32), "vcg_gemm_batched: batch stride overflow");
-  int bm, bn, nsplit, kt_per;
-  gemm_plan(rows, Ncols, (K + BK - 1) / BK, false, bm, bn, nsplit, kt_per, batches, false, K <= 2048);
-  dim3 grid((rows + bm - 1) / bm, (Ncols + bn - 1) / bn, batches);
-  {
-    VcgProfScope prof("k_conv_fwd<fp32 MFMA>", 2.0 * rows * (double)K * Ncols * batches, st);
-    if (bm == 128 && bn == 128 && K <= 2048) hipLaunchKernelGGL((k_conv_fwd<128, 128, 2, false>), grid, dim3(256), 0, st, p);
-    else DISPATCH_FWD(bm, bn, grid, st, p);
-  }
-  VCG_LAUNCH_CHECK("vcg_gemm_batched");
-  return 0;
-}
-
-// floats of the packed-weight buffer: Wf[K][Cout], then (3x3 stride-1 layers) the Winograd-transformed U[16][Kc][Cout]
-static size_t wf_floats(const ConvGeom& g) { return (((size_t)g.K * g.Cout + 63) / 64) * 64; }
-// offset of Wkd (kw-folded thin data gradient) in the packed buffer: after Wf and, for a 4 -> 4 layer, after Wk
+// ---- launch plans ---------------------------------------------------------------------------------------------------------
+// Which kernels a descriptor runs on is decided here and nowhere else: plan_fwd, plan_dgrad and plan_wgrad each walk their chain
+// once (first match wins), and the size queries and the launches below read what they return.
+//   forward        thin-fold (kw folded into N: the 64 -> 3 7x7 head) -> thin (Cout == 4) -> thinin (the 3 -> 64 4x4 s2 discriminator
+//                  stem) -> Winograd -> LDS slab -> split-operand tile from the WFT planes -> fp32 tile; the tiles may slice K
+//   data gradient  unsupported (map not divisible by the stride) -> thin-fold (the 3 -> 64 7x7 stem) -> thin (Cin == 4) -> Winograd
+//                  over the padded domain -> LDS slab -> split-operand tile from the WFD planes -> 32-column split tile -> 128 x 64
+//                  split tile without planes -> fp32 tile; stride 2 runs s * s parity classes, re-planned as batches if too few
+//   weight grad.   Winograd -> row ring -> stream-K with swapped roles (Cout == 4) -> stream-K; the last two end in a scatter or
+//                  reduce kernel, behind k_slab_sum where a tile has more than kMaxDirectSlabs parts
+//
 // The direct split-operand kernels take their weight operand pre-split (k_pack_planes): the forward the WFT planes, the data
 // gradient the WFD planes.  Layers that own Winograd copies (every D, R and U block from 128 reduction channels on) run
 // through those in all three directions and get neither; should one of them meet a map Winograd cannot take (odd sizes), it
@@ -2074,59 +2048,171 @@ static size_t wf_floats(const ConvGeom& g) { return (((size_t)g.K * g.Cout + 63)
 // (a layer with Winograd copies whose channel product is under a direction's gate — kWinoGateFwd / kWinoGateDgrad, vcg_common.h:
 // forward from Kc Cout / (Kc + Cout) = 100, data gradient from 80; the 1024 -> 64 latent convs sit at 60 — runs that direction
 // direct, and gets the planes for it)
-static bool wino_takes_fwd(const ConvGeom& g) {
+static bool wino_takes(const ConvGeom& g, long long gate) {
   const long long kc = (long long)g.ups * g.ups * g.Cin;
-  return vcg_wino_weight_ok(g) && kc * g.Cout >= kWinoGateFwd * (kc + g.Cout);
+  return vcg_wino_weight_ok(g) && kc * g.Cout >= gate * (kc + g.Cout);
 }
-static bool wino_takes_dgrad(const ConvGeom& g) {
-  const long long kc = (long long)g.ups * g.ups * g.Cin;
-  return vcg_wino_weight_ok(g) && kc * g.Cout >= kWinoGateDgrad * (kc + g.Cout);
-}
-// floats of the Winograd copies a layer keeps: U if some map can take the forward (and with it the weight gradient), Ud if
-// some map can take the data gradient
-static size_t wino_u_floats(const ConvGeom& g) { return wino_takes_fwd(g) ? vcg_wino_weight_floats(g) : 0; }
-static size_t wino_ud_floats(const ConvGeom& g) { return wino_takes_dgrad(g) ? vcg_wino_weight_floats(g) : 0; }
+static bool wino_takes_fwd(const ConvGeom& g) { return wino_takes(g, kWinoGateFwd); }
+static bool wino_takes_dgrad(const ConvGeom& g) { return wino_takes(g, kWinoGateDgrad); }
 static bool wft_wanted(const ConvGeom& g) { return g.Cout >= 64 && g.Cin % 4 == 0 && !wino_takes_fwd(g); }
 static bool wfd_wanted(const ConvGeom& g) {
   return g.Cout >= 64 && g.Cout % 32 == 0 && !wino_takes_dgrad(g) && !vcg_thin_fold_dgrad_ok(g) && !vcg_thin_dgrad_ok(g);
 }
-static size_t wft_floats(const ConvGeom& g) { return (size_t)g.Cout * ((g.K + 31) / 32) * VCG_PFLOATS; }      // VCG_PBYTES per (co, K block)
-static size_t wfd_floats(const ConvGeom& g) { return (size_t)g.KH * g.KW * g.ups * g.ups * g.Cin * (g.Cout / 32) * VCG_PFLOATS; }
-static size_t wkd_offset(const ConvGeom& g) { return wf_floats(g) + (vcg_thin_fold_ok(g) ? vcg_thin_fold_weight_floats(g) : 0); }
-static size_t wft_offset(const ConvGeom& g) {
-  return wf_floats(g) + wino_u_floats(g) + wino_ud_floats(g) +
-         (vcg_thin_fold_ok(g) ? vcg_thin_fold_weight_floats(g) : 0) +
-         (vcg_thin_fold_dgrad_ok(g) ? vcg_thin_fold_dgrad_weight_floats(g) : 0);
+
+// The packed-weight buffer, offsets in floats, in this order: Wf[K][Cout] in fp32 (rounded up to 64 floats); U and Ud, the
+// Winograd-transformed kernels of the forward (and with it the weight gradient) and of the data gradient, kept if some map can
+// take that direction; Wk and Wkd, the kw-folded copies of the thin forward and the thin data gradient; the WFT and WFD planes
+// (VCG_PBYTES per (co, K block) / per (K row, 32 outputs)); a 16-float header whose word 0 is the bit pattern of the kernel's
+// largest magnitude (what every plane set of the pack was scaled by: vcg_common.h).  A section the layer does not keep is
+// empty, so its size is the next offset minus its own.  Winograd copies and thin-fold copies never meet in one pack: the folds
+// need a 4-channel side (Cout == 4, or Cin == 4 with ups == 1), the Winograd weight gate Cout >= 64 and ups^2 Cin >= 128.
+struct PackLayout { size_t wf, u, ud, wk, wkd, wft, wfd, hdr, total; };
+static PackLayout pack_layout(const ConvGeom& g) {
+  PackLayout L;
+  size_t o = 0;
+  L.wf = o;  o += (((size_t)g.K * g.Cout + 63) / 64) * 64;
+  L.u = o;   if (wino_takes_fwd(g)) o += vcg_wino_weight_floats(g);
+  L.ud = o;  if (wino_takes_dgrad(g)) o += vcg_wino_weight_floats(g);
+  L.wk = o;  if (vcg_thin_fold_ok(g)) o += vcg_thin_fold_weight_floats(g);
+  L.wkd = o; if (vcg_thin_fold_dgrad_ok(g)) o += vcg_thin_fold_dgrad_weight_floats(g);
+  L.wft = o; if (wft_wanted(g)) o += (size_t)g.Cout * ((g.K + 31) / 32) * VCG_PFLOATS;
+  L.wfd = o; if (wfd_wanted(g)) o += (size_t)g.K * (g.Cout / 32) * VCG_PFLOATS;
+  L.hdr = o; L.total = o + 16;
+  return L;
 }
-static size_t wfd_offset(const ConvGeom& g) { return wft_offset(g) + (wft_wanted(g) ? wft_floats(g) : 0); }
-// the pack ends with a 16-float header: word 0 = bit pattern of the kernel's largest magnitude (what every plane set of
-// the pack was scaled by: vcg_common.h), read by the kernels that multiply by those planes
-static size_t wamax_offset(const ConvGeom& g) { return wfd_offset(g) + (wfd_wanted(g) ? wfd_floats(g) : 0); }
-const void* vcg_pack_amax(const ConvGeom& g, const float* wf) { return wf + wamax_offset(g); }
-// the row-ring weight gradients (conv_ring.hip)
-static bool wgrad_ring_ok(const ConvGeom& g) { return !vcg_wino_wgrad_ok(g) && vcg_ring_wgrad_ok(g); }
-// the slab kernels (conv_slab.hip)
-static bool fwd_slab_ok(const ConvGeom& g) {
-  return !vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && !vcg_wino_fwd_ok(g) && wft_wanted(g) && vcg_slab_fwd_ok(g);
+
+enum FwdPath { FWD_THIN_FOLD, FWD_THIN, FWD_THININ, FWD_WINO, FWD_SLAB, FWD_SPLIT, FWD_FP32 };
+struct FwdPlan {
+  FwdPath path;
+  Tile t;                  // SPLIT, FP32
+  bool single_level;       // FP32 at 128 x 128: the kernel without the second accumulator set (K <= 2048)
+  size_t ws;               // bytes of conv workspace
+  // the InstanceNorm statistics of y (vcg_conv_fwd_in).  stats_nchunk > 0: the conv's own epilogue leaves that many chunk
+  // partials per image and only vcg_in_finalize follows; 0: y is reduced by the pass vcg_in_stats runs
+  int stats_nchunk;
+  size_t part_bytes;       // the partials, or that pass's workspace
+  bool reads_wf;           // the fp32 Wf block of the pack is read
+  bool pre_ok;             // the input gather can normalise on the fly (vcg_conv_fwd_in_pre)
+  size_t saved_floats;     // forward state worth keeping for the weight gradient (the Winograd-transformed input V)
+};
+static FwdPlan plan_fwd(const ConvGeom& g) {
+  FwdPlan pl = {};
+  if (vcg_thin_fold_ok(g)) { pl.path = FWD_THIN_FOLD; pl.ws = vcg_thin_fold_workspace(g); }
+  else if (vcg_thin_fwd_ok(g)) { pl.path = FWD_THIN; pl.reads_wf = true; }
+  else if (vcg_thinin_fwd_ok(g)) { pl.path = FWD_THININ; pl.reads_wf = true; pl.stats_nchunk = vcg_thinin_nchunk(g); }
+  else if (vcg_wino_fwd_ok(g)) {
+    pl.path = FWD_WINO; pl.ws = vcg_wino_fwd_workspace(g); pl.pre_ok = true; pl.saved_floats = vcg_wino_saved_floats(g);
+    pl.stats_nchunk = (int)(vcg_wino_fwd_stats_doubles(g) / ((size_t)g.N * g.Cout * 2));
+  } else if (wft_wanted(g) && vcg_slab_fwd_ok(g)) {
+    pl.path = FWD_SLAB;
+    if (vcg_slab_fwd_stats_ok(g)) pl.stats_nchunk = vcg_slab_fwd_nchunk(g);
+  } else {
+    pl.t = gemm_plan(g.M, g.Cout, (g.K + BK - 1) / BK, true, 1, true);
+    const bool split = pl.t.bm == 128 && pl.t.bn >= 64 && wft_wanted(g);
+    pl.path = split ? FWD_SPLIT : FWD_FP32; pl.single_level = g.K <= 2048; pl.reads_wf = !split;
+    if (pl.t.nsplit > 1) pl.ws = (size_t)pl.t.nsplit * g.M * g.Cout * sizeof(float) + 256;
+    // the split-operand tile leaves the partials itself where every 128-row tile lies inside one image
+    if (split && pl.t.nsplit == 1 && (g.Ho * g.Wo) % 128 == 0) pl.stats_nchunk = g.Ho * g.Wo / 128;
+  }
+  pl.part_bytes = pl.stats_nchunk ? (size_t)g.N * pl.stats_nchunk * g.Cout * 2 * sizeof(double)
+                                  : vcg_in_workspace(g.N, g.Ho * g.Wo, g.Cout);
+  return pl;
 }
-static bool dgrad_slab_ok(const ConvGeom& g) {
-  return !vcg_thin_fold_dgrad_ok(g) && !vcg_thin_dgrad_ok(g) && !vcg_wino_dgrad_ok(g) && wfd_wanted(g) && vcg_slab_dgrad_ok(g);
+
+// SPLIT_PLANES: 128 x 128 / 64, weight rows from the pre-split WFD planes of the pack.  Layers without planes (the 4-channel dy
+// of the 7x7 head: K = (tap, co) is not a multiple of 32 per tap) still run on the 16-bit pipe when their tile is 128 x 64
+// (SPLIT64_NOPLANES: the weight rows are split in the kernel from Wf) or 32 columns wide (SPLIT32)
+enum DgradPath { DGRAD_UNSUPPORTED, DGRAD_THIN_FOLD, DGRAD_THIN, DGRAD_WINO, DGRAD_SLAB, DGRAD_SPLIT_PLANES, DGRAD_SPLIT32,
+                 DGRAD_SPLIT64_NOPLANES, DGRAD_FP32 };
+struct DgradPlan {
+  DgradPath path;
+  Tile t;                  // the four tile paths; nsplit counts the K slices of one parity class
+  bool replan;             // stride 2: planned again with the s * s parity classes as batches
+  size_t ws;
+  bool reads_wf;
+};
+static DgradPlan plan_dgrad(const ConvGeom& g) {
+  DgradPlan pl = {};
+  const int s = g.stride;
+  const bool wfd = wfd_wanted(g);
+  if (g.Hl % s || g.Wl % s) { pl.path = DGRAD_UNSUPPORTED; pl.reads_wf = true; }
+  else if (vcg_thin_fold_dgrad_ok(g)) { pl.path = DGRAD_THIN_FOLD; pl.ws = vcg_thin_fold_dgrad_workspace(g); }
+  else if (vcg_thin_dgrad_ok(g)) { pl.path = DGRAD_THIN; pl.ws = vcg_thin_dgrad_workspace(g); pl.reads_wf = true; }
+  else if (vcg_wino_dgrad_ok(g)) { pl.path = DGRAD_WINO; pl.ws = vcg_wino_dgrad_workspace(g); }
+  else if (wfd && vcg_slab_dgrad_ok(g)) { pl.path = DGRAD_SLAB; pl.ws = vcg_slab_dgrad_workspace(g); }
+  else {
+    // stride s: s * s parity classes, each a GEMM over its own (KH / s) x (KW / s) taps — the planner sees them as batches,
+    // and blockIdx.z = class + s * s * K slice
+    const int Mc = g.N * (g.Hl / s) * (g.Wl / s), NB = g.ups * g.ups * g.Cin;
+    pl.t = gemm_plan(Mc, NB, (g.KH * g.KW * g.Cout + BK - 1) / BK, s == 1, 1, true);
+    if (s > 1 && g.KH % s == 0 && g.KW % s == 0) {
+      // the unsliced plan fills the chip for the large maps (measured: slicing made 64 -> 128 at 128^2 and 128 -> 256 at 64^2
+      // slower); the deep layer (256 -> 512 at 32^2: 256 workgroups) is the one that needs its K cut
+      const long long wgs = ((Mc + pl.t.bm - 1) / pl.t.bm) * ((NB + pl.t.bn - 1) / pl.t.bn) * s * s;
+      pl.replan = wgs < 384;
+      if (pl.replan) pl.t = gemm_plan(Mc, NB, ((g.KH / s) * (g.KW / s) * g.Cout + BK - 1) / BK, true, s * s, true);
+    }
+    const bool planes = pl.t.bm == 128 && pl.t.bn >= 64 && wfd;
+    pl.path = planes ? DGRAD_SPLIT_PLANES : pl.t.bn == 32 ? DGRAD_SPLIT32
+              : pl.t.bm == 128 && pl.t.bn == 64 ? DGRAD_SPLIT64_NOPLANES : DGRAD_FP32;
+    pl.reads_wf = !planes;
+    if (pl.t.nsplit > 1) pl.ws = (size_t)pl.t.nsplit * g.N * g.H * g.W * g.Cin * sizeof(float) + 256;
+  }
+  return pl;
+}
+
+// a tile kernel and the name the profile table (vcg_profile_read) lists it under
+typedef void (*ConvKernel)(ConvP);
+struct KernelRef { ConvKernel fn; const char* name; };
+
+// the fp32-MFMA forward tiles.  single_level: the 128 x 128 kernel without the second accumulator set
+static KernelRef fwd_fp32_kernel(const Tile& t, bool single_level) {
+  const char* const name = "k_conv_fwd<fp32 MFMA>";
+  if (t.bm == 128 && t.bn == 128 && single_level) return {k_conv_fwd<128, 128, 2, false>, name};
+  if (t.bn == 32) return {k_conv_fwd<128, 32, 1>, name};
+  if (t.bm == 128 && t.bn == 128) return {k_conv_fwd<128, 128>, name};
+  if (t.bm == 128 && t.bn == 64) return {k_conv_fwd<128, 64>, name};
+  if (t.bm == 64 && t.bn == 128) return {k_conv_fwd<64, 128>, name};
+  return {k_conv_fwd<64, 64>, name};
+}
+// one tile launch of the forward: blockIdx.z = batch (vcg_gemm_batched) or K slice
+static void launch_fwd_tile(const Tile& t, const KernelRef& k, const ConvP& p, hipStream_t st) {
+  dim3 grid((p.M + t.bm - 1) / t.bm, (p.Cout + t.bn - 1) / t.bn, p.nbatch * p.ksplit);
+  VcgProfScope prof(k.name, 2.0 * p.M * (double)p.K * p.Cout * p.nbatch, st);
+  hipLaunchKernelGGL(k.fn, grid, dim3(256), 0, st, p);
+}
+
+static ConvGeom gemm_geom(int rows, int K, int Ncols) {       // a plain GEMM as a 1x1 convolution over one row of `rows` pixels
+  ConvGeom g = {};
+  g.N = 1; g.H = 1; g.W = rows; g.Cin = K; g.Cout = Ncols; g.KH = g.KW = 1; g.stride = 1; g.pad = 0; g.reflect = 0;
+  g.ups = 1; g.act = VCG_ACT_NONE; g.cin_log = K; g.cout_log = Ncols;
+  g.Hl = 1; g.Wl = rows; g.Ho = 1; g.Wo = rows; g.M = rows; g.K = K; g.taps = 1;
+  return g;
+}
+// C[z][m][n] = sum_k A[z][m][k] * B[z][k][n]   (row-major, k and n multiples of 4) — the forward kernel run as a
+// 1x1 convolution over `rows` pixels, one batch per blockIdx.z.  Used by the Winograd path (conv_wino.hip).
+int vcg_gemm_batched(const float* A, const float* B, float* C, int rows, int K, int Ncols, int batches, hipStream_t st) {
+  ConvP p; fill_params(gemm_geom(rows, K, Ncols), p);
+  p.a = A; p.b = B; p.bias = nullptr; p.out = C;
+  if (set_extents(p, (unsigned long long)rows * K * 4, (unsigned long long)K * Ncols * 4,
+                  "vcg_gemm_batched: operand extents must stay below 2 GiB per batch")) return -1;
+  p.nbatch = batches; p.a_bstride = (uint32_t)((size_t)rows * K); p.b_bstride = (uint32_t)((size_t)K * Ncols);
+  p.out_bstride = (size_t)rows * Ncols;
+  VCG_CHECK_ARG((unsigned long long)rows * K * (unsigned long long)batches < (1ull << 32), "vcg_gemm_batched: batch stride overflow");
+  const Tile t = gemm_plan(rows, Ncols, (K + BK - 1) / BK, false, batches, false, K <= 2048);
+  launch_fwd_tile(t, fwd_fp32_kernel(t, K <= 2048), p, st);
+  VCG_LAUNCH_CHECK("vcg_gemm_batched");
+  return 0;
 }
 
 // the forward kernel on a caller-built geometry (no bias, no activation, no K slicing): conv_thin.hip's kw-folded path
 int vcg_fwd_launch(const ConvGeom& g, const float* x, const float* wf, float* y, hipStream_t st) {
   ConvP p; fill_params(g, p);
   p.a = x; p.b = wf; p.bias = nullptr; p.out = y; p.act = VCG_ACT_NONE;
-  const unsigned long long ab = (unsigned long long)g.N * g.H * g.W * g.Cin * 4, bb = (unsigned long long)g.K * g.Cout * 4;
-  VCG_CHECK_ARG(ab < (1ull << 31) && bb < (1ull << 31), "vcg_conv_fwd: tensor extents must stay below 2 GiB");
-  p.a_bytes = (uint32_t)ab; p.b_bytes = (uint32_t)bb;
-  int bm, bn, nsplit, kt_per;
-  gemm_plan(g.M, g.Cout, (g.K + BK - 1) / BK, false, bm, bn, nsplit, kt_per, 1, true);
-  dim3 grid((g.M + bm - 1) / bm, (g.Cout + bn - 1) / bn, 1);
-  {
-    VcgProfScope prof("k_conv_fwd<fp32 MFMA>", 2.0 * g.M * (double)g.K * g.Cout, st);
-    DISPATCH_FWD(bm, bn, grid, st, p);
-  }
+  if (set_extents(p, (unsigned long long)g.N * g.H * g.W * g.Cin * 4, (unsigned long long)g.K * g.Cout * 4,
+                  "vcg_conv_fwd: tensor extents must stay below 2 GiB")) return -1;
+  const Tile t = gemm_plan(g.M, g.Cout, (g.K + BK - 1) / BK, false, 1, true);
+  launch_fwd_tile(t, fwd_fp32_kernel(t, false), p, st);
   VCG_LAUNCH_CHECK("vcg_conv_fwd(raw)");
   return 0;
 }
@@ -2134,82 +2220,59 @@ int vcg_fwd_launch(const ConvGeom& g, const float* x, const float* wf, float* y,
 extern "C" size_t vcg_pack_weight_floats(const int32_t* cd) {
   ConvGeom g;
   if (vcg_conv_geom(cd, &g, "vcg_pack_weight_floats")) return 0;
-  return wf_floats(g) + wino_u_floats(g) + wino_ud_floats(g)                           // + U (forward) + Ud (data gradient)
-         + (vcg_thin_fold_ok(g) ? vcg_thin_fold_weight_floats(g) : 0)                   // + Wk (kw-folded thin forward)
-         + (vcg_thin_fold_dgrad_ok(g) ? vcg_thin_fold_dgrad_weight_floats(g) : 0)       // + Wkd (kw-folded thin data gradient)
-         + (wft_wanted(g) ? wft_floats(g) : 0)                                          // + WFT planes (split-operand direct forward)
-         + (wfd_wanted(g) ? wfd_floats(g) : 0)                                          // + WFD planes (split-operand direct data gradient)
-         + 16;                                                                          // + the header (wamax_offset)
+  return pack_layout(g).total;
 }
 
 extern "C" int vcg_pack_weight(const float* w_oihw, float* wf, const int32_t* cd, void* stream) {
   ConvGeom g;
   if (vcg_conv_geom(cd, &g, "vcg_pack_weight")) return -1;
   VCG_CHECK_ARG(w_oihw && wf, "vcg_pack_weight: null pointer");
+  const PackLayout L = pack_layout(g);
+  hipStream_t st = (hipStream_t)stream;
   // the kernel's largest magnitude: every pre-split plane set below holds w / s (vcg_common.h), and the header keeps the
   // bits for the kernels that consume the planes
-  const VcgAmaxOut aw = vcg_amax_new((hipStream_t)stream);
-  if (vcg_absmax_launch(w_oihw, (size_t)g.cout_log * g.cin_log * g.ups * g.ups * g.KH * g.KW, aw, (hipStream_t)stream)) return -2;
+  const VcgAmaxOut aw = vcg_amax_new(st);
+  if (vcg_absmax_launch(w_oihw, (size_t)g.cout_log * g.cin_log * g.ups * g.ups * g.KH * g.KW, aw, st)) return -2;
   const VcgAmax amax_w = vcg_amax_in(aw);                  // the header word is written by the Wf pack kernel at the end of this call
-  if (vcg_thin_fold_ok(g) && vcg_thin_fold_pack(g, w_oihw, wf + wf_floats(g), amax_w, (hipStream_t)stream)) return -2;
-  if (vcg_thin_fold_dgrad_ok(g) && vcg_thin_fold_dgrad_pack(g, w_oihw, wf + wkd_offset(g), amax_w, (hipStream_t)stream)) return -2;
-  if (wft_wanted(g)) {
-    ConvP q; fill_params(g, q);
-    q.amax_b = amax_w;
-    const size_t tot = (size_t)g.Cout * ((g.K + 31) / 32) * 8;
-    int blocks = (int)((tot + 255) / 256); if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_pack_planes<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)(wf + wft_offset(g)), q,
-                       g.cin_log, g.cout_log);
-    VCG_LAUNCH_CHECK("vcg_pack_weight(WFT planes)");
-  }
-  if (wfd_wanted(g)) {
-    ConvP q; fill_params(g, q);
-    q.amax_b = amax_w;
-    const size_t tot = (size_t)g.KH * g.KW * g.ups * g.ups * g.Cin * (g.Cout / 4);
-    int blocks = (int)((tot + 255) / 256); if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_pack_planes<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, (unsigned short*)(wf + wfd_offset(g)), q,
-                       g.cin_log, g.cout_log);
-    VCG_LAUNCH_CHECK("vcg_pack_weight(WFD planes)");
-  }
-  if (wino_takes_fwd(g) && vcg_wino_weight(g, w_oihw, wf + wf_floats(g), amax_w, (hipStream_t)stream)) return -2;
-  if (wino_takes_dgrad(g) && vcg_wino_weight_dgrad(g, w_oihw, wf + wf_floats(g) + wino_u_floats(g), amax_w, (hipStream_t)stream)) return -2;
   ConvP p; fill_params(g, p);
   p.amax_b = amax_w;
-  uint32_t* const hdr = (uint32_t*)(wf + wamax_offset(g));
+  // each section the layout keeps (it is not empty: the next offset lies behind its own)
+  if (L.wkd > L.wk && vcg_thin_fold_pack(g, w_oihw, wf + L.wk, amax_w, st)) return -2;
+  if (L.wft > L.wkd && vcg_thin_fold_dgrad_pack(g, w_oihw, wf + L.wkd, amax_w, st)) return -2;
+  if (L.wfd > L.wft) {
+    const size_t tot = (size_t)g.Cout * ((g.K + 31) / 32) * 8;
+    int blocks = (int)((tot + 255) / 256); if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_pack_planes<false>, dim3(blocks), dim3(256), 0, st, w_oihw, (unsigned short*)(wf + L.wft), p, g.cin_log,
+                       g.cout_log);
+    VCG_LAUNCH_CHECK("vcg_pack_weight(WFT planes)");
+  }
+  if (L.hdr > L.wfd) {
+    const size_t tot = (size_t)g.K * (g.Cout / 4);
+    int blocks = (int)((tot + 255) / 256); if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_pack_planes<true>, dim3(blocks), dim3(256), 0, st, w_oihw, (unsigned short*)(wf + L.wfd), p, g.cin_log,
+                       g.cout_log);
+    VCG_LAUNCH_CHECK("vcg_pack_weight(WFD planes)");
+  }
+  if (L.ud > L.u && vcg_wino_weight(g, w_oihw, wf + L.u, amax_w, st)) return -2;
+  if (L.wk > L.ud && vcg_wino_weight_dgrad(g, w_oihw, wf + L.ud, amax_w, st)) return -2;
+  uint32_t* const hdr = (uint32_t*)(wf + L.hdr);
   if (cd[VCG_CD_PACK_FLAGS] & 1) {                          // the caller knows nothing reads Wf (vcg_conv_reads_wf): the header only
     ConvP q = p; q.K = 0; q.Cout = 0;
-    hipLaunchKernelGGL(k_pack_weight, dim3(1), dim3(64), 0, (hipStream_t)stream, w_oihw, wf, q, g.cin_log, g.cout_log, hdr);
+    hipLaunchKernelGGL(k_pack_weight, dim3(1), dim3(64), 0, st, w_oihw, wf, q, g.cin_log, g.cout_log, hdr);
     VCG_LAUNCH_CHECK("vcg_pack_weight(header)");
     return 0;
   }
   size_t total = (size_t)g.K * g.Cout;
-  const int T = g.KH * g.KW * g.ups * g.ups;
-  const size_t lds = (size_t)T * 8 * 33 * sizeof(float);
+  const size_t lds = (size_t)g.taps * 8 * 33 * sizeof(float);
   if (total < (1u << 20) || lds > 64 * 1024) {
     int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_pack_weight, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w_oihw, wf, p, g.cin_log, g.cout_log, hdr);
+    hipLaunchKernelGGL(k_pack_weight, dim3(blocks), dim3(256), 0, st, w_oihw, wf, p, g.cin_log, g.cout_log, hdr);
   } else {
-    hipLaunchKernelGGL(k_pack_weight_t, dim3((g.Cout + 31) / 32, (g.Cin + 7) / 8), dim3(256), lds, (hipStream_t)stream,
-                       w_oihw, wf, p, g.cin_log, g.cout_log, hdr);
+    hipLaunchKernelGGL(k_pack_weight_t, dim3((g.Cout + 31) / 32, (g.Cin + 7) / 8), dim3(256), lds, st, w_oihw, wf, p, g.cin_log,
+                       g.cout_log, hdr);
   }
   VCG_LAUNCH_CHECK("vcg_pack_weight");
   return 0;
-}
-
-static void fwd_plan(const ConvGeom& g, int& bm, int& bn, int& nsplit, int& kt_per) {
-  gemm_plan(g.M, g.Cout, (g.K + BK - 1) / BK, true, bm, bn, nsplit, kt_per, 1, true);
-}
-
-extern "C" size_t vcg_conv_fwd_workspace(const int32_t* cd) {
-  ConvGeom g;
-  if (vcg_conv_geom(cd, &g, "vcg_conv_fwd_workspace")) return 0;
-  if (vcg_thin_fold_ok(g)) return vcg_thin_fold_workspace(g);
-  if (vcg_thin_fwd_ok(g) || vcg_thinin_fwd_ok(g)) return 0;
-  if (vcg_wino_fwd_ok(g)) return vcg_wino_fwd_workspace(g);
-  if (fwd_slab_ok(g)) return 0;
-  int bm, bn, nsplit, kt_per;
-  fwd_plan(g, bm, bn, nsplit, kt_per);
-  return nsplit > 1 ? (size_t)nsplit * g.M * g.Cout * sizeof(float) + 256 : 0;
 }
 
 static int ew_grid(size_t work) {
@@ -2218,104 +2281,85 @@ static int ew_grid(size_t work) {
   return b < 1 ? 1 : (int)b;
 }
 
-// does the direct split-operand forward leave the InstanceNorm partials itself?  (every 128-row tile inside one image)
-static bool fwd_tile_stats_ok(const ConvGeom& g) {
-  if (vcg_thin_fold_ok(g) || vcg_thin_fwd_ok(g) || vcg_thinin_fwd_ok(g) || vcg_wino_fwd_ok(g) || fwd_slab_ok(g)) return false;
-  int bm, bn, nsplit, kt_per;
-  fwd_plan(g, bm, bn, nsplit, kt_per);
-  return bm == 128 && bn >= 64 && nsplit == 1 && wft_wanted(g) && (g.Ho * g.Wo) % 128 == 0;
+static KernelRef fwd_kernel(const FwdPlan& pl) {
+  if (pl.path == FWD_FP32) return fwd_fp32_kernel(pl.t, pl.single_level);
+  if (pl.t.bn == 128) return {k_conv_fwd_split<128>, "k_conv_fwd_split<128>"};      // FWD_SPLIT: B^T from the WFT planes
+  return {k_conv_fwd_split<64>, "k_conv_fwd_split<64>"};
 }
 
-// in_part != nullptr: also leave the InstanceNorm chunk partials of y there (the caller checked that this launch plan
-// can: Winograd, or fwd_tile_stats_ok) and report the chunk count per image.
-static int conv_fwd_impl(const float* x, const float* wf, const float* bias, float* y, const int32_t* cd, void* ws,
-                         size_t ws_bytes, void* stream, double* in_part, const VcgInStatsOut* stats, float* saved = nullptr,
-                         const VcgPre* pre = nullptr) {
-  const uint64_t x_handle = vcg_take_hint_x();              // vcg_amax_hint: who wrote x left its largest magnitude (or 0)
-  (void)vcg_take_hint_dy();
-  ConvGeom g;
-  if (vcg_conv_geom(cd, &g, "vcg_conv_fwd")) return -1;
+// vcg_amax_hint: who wrote x left its largest magnitude (or 0); a forward has no use for the one of dy
+static uint64_t take_fwd_hints() {
+  const uint64_t x_handle = vcg_take_hint_x(); (void)vcg_take_hint_dy();
+  return x_handle;
+}
+
+// in_part != nullptr: also leave the InstanceNorm chunk partials of y there (the caller saw pl.stats_nchunk > 0) and combine
+// them into stats->mean / rstd.
+static int conv_fwd_impl(const ConvGeom& g, const FwdPlan& pl, uint64_t x_handle, const float* x, const float* wf, const float* bias,
+                         float* y, void* ws, size_t ws_bytes, void* stream, double* in_part, const VcgInStatsOut* stats,
+                         float* saved = nullptr, const VcgPre* pre = nullptr) {
   VCG_CHECK_ARG(x && wf && y, "vcg_conv_fwd: null pointer");
   if (pre && pre->mean)
-    VCG_CHECK_ARG(!vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && vcg_wino_fwd_ok(g),
-                  "vcg_conv_fwd_in_pre: this geometry has no normalising gather (ask vcg_conv_pre_ok first)");
-  if (vcg_thin_fold_ok(g)) return vcg_thin_fold_fwd(g, x, wf + wf_floats(g), vcg_pack_amax(g, wf), bias, y, ws, ws_bytes, (hipStream_t)stream, x_handle);
-  if (vcg_thin_fwd_ok(g)) return vcg_thin_fwd(g, x, wf, bias, y, (hipStream_t)stream);
-  if (vcg_thinin_fwd_ok(g)) {
-    if (vcg_thinin_fwd(g, x, wf, vcg_pack_amax(g, wf), bias, y, in_part, (hipStream_t)stream, x_handle)) return -2;
-    if (in_part)
-      return vcg_in_finalize(in_part, stats->mean, stats->rstd, g.N, stats->HW, g.Cout, vcg_thinin_nchunk(g), stats->eps, (hipStream_t)stream);
-    return 0;
-  }
-  if (vcg_wino_fwd_ok(g))
-    return vcg_wino_fwd(g, x, wf + wf_floats(g), vcg_pack_amax(g, wf), bias, y, ws, ws_bytes, (hipStream_t)stream, in_part, stats, saved, x_handle,
-                        pre);
-  if (fwd_slab_ok(g))
-    return vcg_slab_fwd(g, x, wf + wft_offset(g), wft_floats(g) * 4, vcg_pack_amax(g, wf), bias, y, in_part, stats, (hipStream_t)stream, x_handle);
-  ConvP p; fill_params(g, p);
-  if (in_part) {
-    p.in_part = in_part;
-    p.in_nchunk = g.Ho * g.Wo / 128;
-  }
-  p.a = x; p.b = wf; p.bias = bias; p.out = y;
-  {
-    const unsigned long long ab = (unsigned long long)g.N * g.H * g.W * g.Cin * 4, bb = (unsigned long long)g.K * g.Cout * 4;
-    VCG_CHECK_ARG(ab < (1ull << 31) && bb < (1ull << 31), "vcg_conv_fwd: tensor extents must stay below 2 GiB");
-    p.a_bytes = (uint32_t)ab; p.b_bytes = (uint32_t)bb;
-  }
-  int bm, bn, nsplit, kt_per;
-  fwd_plan(g, bm, bn, nsplit, kt_per);
-  if (nsplit > 1) {
-    VCG_CHECK_ARG(ws && ws_bytes >= vcg_conv_fwd_workspace(cd), "vcg_conv_fwd: workspace too small (%zu)", ws_bytes);
-    p.ksplit = nsplit; p.kt_per = kt_per; p.slab = (float*)ws;
-  }
-  dim3 grid((g.M + bm - 1) / bm, (g.Cout + bn - 1) / bn, nsplit);
+    VCG_CHECK_ARG(pl.pre_ok, "vcg_conv_fwd_in_pre: this geometry has no normalising gather (ask vcg_conv_pre_ok first)");
+  const PackLayout L = pack_layout(g);
+  const void* const w_amax = wf + L.hdr;
   hipStream_t st = (hipStream_t)stream;
-  const double gemm_flops = 2.0 * g.M * (double)g.K * g.Cout;
-  if (bm == 128 && bn >= 64 && wft_wanted(g)) {          // split-operand fp16 kernel, B^T from the pre-split WFT planes of the pack
-    p.b = wf + wft_offset(g);
-    p.b_bytes = (uint32_t)(wft_floats(g) * 4);
+  auto finalize = [&]() {      // the partials of this launch -> mean / rstd (Winograd and the slab kernels do it themselves)
+    return in_part ? vcg_in_finalize(in_part, stats->mean, stats->rstd, g.N, stats->HW, g.Cout, pl.stats_nchunk, stats->eps, st) : 0;
+  };
+  if (pl.path == FWD_THIN_FOLD) return vcg_thin_fold_fwd(g, x, wf + L.wk, w_amax, bias, y, ws, ws_bytes, st, x_handle);
+  if (pl.path == FWD_THIN) return vcg_thin_fwd(g, x, wf, bias, y, st);
+  if (pl.path == FWD_THININ) return vcg_thinin_fwd(g, x, wf, w_amax, bias, y, in_part, st, x_handle) ? -2 : finalize();
+  if (pl.path == FWD_WINO) return vcg_wino_fwd(g, x, wf + L.u, w_amax, bias, y, ws, ws_bytes, st, in_part, stats, saved, x_handle, pre);
+  if (pl.path == FWD_SLAB) return vcg_slab_fwd(g, x, wf + L.wft, (L.wfd - L.wft) * 4, w_amax, bias, y, in_part, stats, st, x_handle);
+  ConvP p; fill_params(g, p);
+  if (in_part) { p.in_part = in_part; p.in_nchunk = pl.stats_nchunk; }
+  p.a = x; p.b = wf; p.bias = bias; p.out = y;
+  if (set_extents(p, (unsigned long long)g.N * g.H * g.W * g.Cin * 4, (unsigned long long)g.K * g.Cout * 4,
+                  "vcg_conv_fwd: tensor extents must stay below 2 GiB")) return -1;
+  const int nsplit = pl.t.nsplit;
+  if (nsplit > 1) {
+    VCG_CHECK_ARG(ws && ws_bytes >= pl.ws, "vcg_conv_fwd: workspace too small (%zu)", ws_bytes);
+    p.ksplit = nsplit; p.kt_per = pl.t.kt_per; p.slab = (float*)ws;
+  }
+  if (pl.path == FWD_SPLIT) {                               // split-operand fp16 kernel, B^T from the pre-split WFT planes of the pack
+    p.b = wf + L.wft;
+    p.b_bytes = (uint32_t)((L.wfd - L.wft) * 4);
     // the input's largest magnitude (its scale, vcg_common.h): from its writer's handle, else measured
     if (vcg_operand_amax(x, (size_t)g.N * g.H * g.W * g.Cin, x_handle, 0, st, &p.amax_a)) return -2;
-    p.amax_b = vcg_amax_stored(vcg_pack_amax(g, wf));
-    VcgProfScope prof(bn == 128 ? "k_conv_fwd_split<128>" : "k_conv_fwd_split<64>", gemm_flops, st);
-    if (bn == 128) hipLaunchKernelGGL((k_conv_fwd_split<128>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_conv_fwd_split<64>), grid, dim3(256), 0, st, p);
-  } else {
-    VcgProfScope prof("k_conv_fwd<fp32 MFMA>", gemm_flops, st);
-    if (bm == 128 && bn == 128 && g.K <= 2048) hipLaunchKernelGGL((k_conv_fwd<128, 128, 2, false>), grid, dim3(256), 0, st, p);
-    else DISPATCH_FWD(bm, bn, grid, st, p);
+    p.amax_b = vcg_amax_stored(w_amax);
   }
+  launch_fwd_tile(pl.t, fwd_kernel(pl), p, st);
   if (nsplit > 1)
     hipLaunchKernelGGL(k_splitk_finish, dim3(ew_grid((size_t)g.M * g.Cout / 4)), dim3(256), 0, st, (const float*)ws, bias,
                        y, (size_t)g.M, g.Cout, nsplit, g.cout_log, g.act);
   VCG_LAUNCH_CHECK("vcg_conv_fwd");
-  if (in_part) return vcg_in_finalize(in_part, stats->mean, stats->rstd, g.N, stats->HW, g.Cout, p.in_nchunk, stats->eps, st);
-  return 0;
+  return finalize();
+}
+
+extern "C" size_t vcg_conv_fwd_workspace(const int32_t* cd) {
+  ConvGeom g;
+  if (vcg_conv_geom(cd, &g, "vcg_conv_fwd_workspace")) return 0;
+  return plan_fwd(g).ws;
 }
 
 extern "C" int vcg_conv_fwd(const float* x, const float* wf, const float* bias, float* y,
                             const int32_t* cd, void* ws, size_t ws_bytes, void* stream) {
-  return conv_fwd_impl(x, wf, bias, y, cd, ws, ws_bytes, stream, nullptr, nullptr);
+  const uint64_t x_handle = take_fwd_hints();
+  ConvGeom g;
+  if (vcg_conv_geom(cd, &g, "vcg_conv_fwd")) return -1;
+  return conv_fwd_impl(g, plan_fwd(g), x_handle, x, wf, bias, y, ws, ws_bytes, stream, nullptr, nullptr);
 }
 
 // ---- convolution + the statistics of the InstanceNorm that follows it (CaSb with norm=True, Networks.py:93-95) ----------
 // Workspace: [conv workspace, rounded to 256 B][statistics partials].  Where the conv's launch plan can, the partial sums
-// come out of the conv's own epilogue (Winograd output transform; the direct split-operand tiles) and only the tiny
-// finalize kernel follows; otherwise y is reduced by the same pass vcg_in_stats runs.
-static size_t fwd_in_conv_ws(const int32_t* cd) { return (vcg_conv_fwd_workspace(cd) + 255) / 256 * 256; }
-
+// come out of the conv's own epilogue (Winograd output transform; the thin-input, slab and direct split-operand tiles) and
+// only the tiny finalize kernel follows; otherwise y is reduced by the same pass vcg_in_stats runs.
 extern "C" size_t vcg_conv_fwd_in_workspace(const int32_t* cd) {
   ConvGeom g;
   if (vcg_conv_geom(cd, &g, "vcg_conv_fwd_in_workspace")) return 0;
-  size_t part;
-  const bool thinin = !vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && vcg_thinin_fwd_ok(g);
-  if (thinin) part = (size_t)g.N * vcg_thinin_nchunk(g) * g.Cout * 2 * sizeof(double);
-  else if (vcg_wino_fwd_ok(g)) part = vcg_wino_fwd_stats_doubles(g) * sizeof(double);
-  else if (fwd_slab_ok(g) && vcg_slab_fwd_stats_ok(g)) part = (size_t)g.N * vcg_slab_fwd_nchunk(g) * g.Cout * 2 * sizeof(double);
-  else if (fwd_tile_stats_ok(g)) part = (size_t)g.N * (g.Ho * g.Wo / 128) * g.Cout * 2 * sizeof(double);
-  else part = vcg_in_workspace(g.N, g.Ho * g.Wo, g.Cout);
-  return fwd_in_conv_ws(cd) + part;
+  const FwdPlan pl = plan_fwd(g);
+  return up256(pl.ws) + pl.part_bytes;
 }
 
 // floats of forward state worth keeping for the weight gradient of this layer (0: nothing) — today the Winograd-transformed
@@ -2323,21 +2367,41 @@ extern "C" size_t vcg_conv_fwd_in_workspace(const int32_t* cd) {
 extern "C" size_t vcg_conv_saved_floats(const int32_t* cd) {
   ConvGeom g;
   if (vcg_conv_geom(cd, &g, "vcg_conv_saved_floats")) return 0;
-  return vcg_wino_fwd_ok(g) ? vcg_wino_saved_floats(g) : 0;
-}
-
-static int conv_fwd_in_impl(const float* x, const float* wf, const float* bias, float* y, float* mean, float* rstd,
-                            float eps, float* saved, const int32_t* cd, void* ws, size_t ws_bytes, void* stream, const VcgPre* pre);
-extern "C" int vcg_conv_fwd_in(const float* x, const float* wf, const float* bias, float* y, float* mean, float* rstd,
-                               float eps, float* saved, const int32_t* cd, void* ws, size_t ws_bytes, void* stream) {
-  return conv_fwd_in_impl(x, wf, bias, y, mean, rstd, eps, saved, cd, ws, ws_bytes, stream, nullptr);
+  return plan_fwd(g).saved_floats;
 }
 // 1 if vcg_conv_fwd_in_pre exists for this geometry: the forward's input gather can normalise on the fly (today: the Winograd
 // input transform — the D2..D4, R and U1 layers at the training sizes)
 extern "C" int vcg_conv_pre_ok(const int32_t* cd) {
   ConvGeom g;
   if (vcg_conv_geom(cd, &g, "vcg_conv_pre_ok")) return 0;
-  return (!vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && vcg_wino_fwd_ok(g)) ? 1 : 0;
+  return plan_fwd(g).pre_ok ? 1 : 0;
+}
+
+static int conv_fwd_in_impl(const float* x, const float* wf, const float* bias, float* y, float* mean, float* rstd,
+                            float eps, float* saved, const int32_t* cd, void* ws, size_t ws_bytes, void* stream, const VcgPre* pre) {
+  ConvGeom g;
+  if (vcg_conv_geom(cd, &g, "vcg_conv_fwd_in")) return -1;
+  VCG_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "vcg_conv_fwd_in: mean and rstd go together");
+  const FwdPlan pl = plan_fwd(g);
+  if (!pl.saved_floats) saved = nullptr;
+  if (!mean) {                                           // no statistics wanted: the plain forward (+ saved state)
+    VCG_CHECK_ARG(ws_bytes >= pl.ws, "vcg_conv_fwd_in: workspace too small (%zu)", ws_bytes);
+    return conv_fwd_impl(g, pl, take_fwd_hints(), x, wf, bias, y, ws, ws_bytes, stream, nullptr, nullptr, saved, pre);
+  }
+  VCG_CHECK_ARG(ws, "vcg_conv_fwd_in: null pointer");
+  const size_t cws = up256(pl.ws);
+  VCG_CHECK_ARG(ws_bytes >= cws + pl.part_bytes, "vcg_conv_fwd_in: workspace too small (%zu)", ws_bytes);
+  double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + cws);
+  // fused: the conv's epilogue leaves the partials, and vcg_in_finalize behind it combines them into mean / rstd
+  const bool fused = pl.stats_nchunk > 0;
+  const VcgInStatsOut stats = {mean, rstd, g.Ho * g.Wo, eps};
+  if (conv_fwd_impl(g, pl, take_fwd_hints(), x, wf, bias, y, ws, cws, stream, fused ? part : nullptr, &stats, saved, pre)) return -1;
+  if (fused) return 0;
+  return vcg_in_stats_pass(y, mean, rstd, g.N, g.Ho * g.Wo, g.Cout, eps, part, ws_bytes - cws, (hipStream_t)stream);
+}
+extern "C" int vcg_conv_fwd_in(const float* x, const float* wf, const float* bias, float* y, float* mean, float* rstd,
+                               float eps, float* saved, const int32_t* cd, void* ws, size_t ws_bytes, void* stream) {
+  return conv_fwd_in_impl(x, wf, bias, y, mean, rstd, eps, saved, cd, ws, ws_bytes, stream, nullptr);
 }
 extern "C" int vcg_conv_fwd_in_pre(const float* t_prev, const float* pre_mean, const float* pre_rstd, int pre_act, const float* wf,
                                    const float* bias, float* y, float* mean, float* rstd, float eps, float* saved, const int32_t* cd,
@@ -2348,85 +2412,42 @@ extern "C" int vcg_conv_fwd_in_pre(const float* t_prev, const float* pre_mean, c
   (void)vcg_take_hint_x();              // the input's magnitude is bounded, not measured (conv_wino.hip, vcg_wino_fwd)
   return conv_fwd_in_impl(t_prev, wf, bias, y, mean, rstd, eps, saved, cd, ws, ws_bytes, stream, &pre);
 }
-static int conv_fwd_in_impl(const float* x, const float* wf, const float* bias, float* y, float* mean, float* rstd,
-                            float eps, float* saved, const int32_t* cd, void* ws, size_t ws_bytes, void* stream, const VcgPre* pre) {
-  ConvGeom g;
-  if (vcg_conv_geom(cd, &g, "vcg_conv_fwd_in")) return -1;
-  VCG_CHECK_ARG((mean == nullptr) == (rstd == nullptr), "vcg_conv_fwd_in: mean and rstd go together");
-  if (saved && !vcg_conv_saved_floats(cd)) saved = nullptr;
-  if (!mean) {                                           // no statistics wanted: the plain forward (+ saved state)
-    VCG_CHECK_ARG(ws_bytes >= vcg_conv_fwd_workspace(cd), "vcg_conv_fwd_in: workspace too small (%zu)", ws_bytes);
-    return conv_fwd_impl(x, wf, bias, y, cd, ws, ws_bytes, stream, nullptr, nullptr, saved, pre);
-  }
-  VCG_CHECK_ARG(ws, "vcg_conv_fwd_in: null pointer");
-  VCG_CHECK_ARG(ws_bytes >= vcg_conv_fwd_in_workspace(cd), "vcg_conv_fwd_in: workspace too small (%zu)", ws_bytes);
-  const size_t cws = fwd_in_conv_ws(cd);
-  double* part = reinterpret_cast<double*>(static_cast<char*>(ws) + cws);
-  const bool thinin = !vcg_thin_fold_ok(g) && !vcg_thin_fwd_ok(g) && vcg_thinin_fwd_ok(g);
-  const bool fused = thinin || vcg_wino_fwd_ok(g) || (fwd_slab_ok(g) && vcg_slab_fwd_stats_ok(g)) || fwd_tile_stats_ok(g);
-  // fused: the conv's epilogue leaves the partials, and vcg_in_finalize behind it combines them into mean / rstd
-  const VcgInStatsOut stats = {mean, rstd, g.Ho * g.Wo, eps};
-  if (conv_fwd_impl(x, wf, bias, y, cd, ws, cws, stream, fused ? part : nullptr, &stats, saved, pre)) return -1;
-  if (fused) return 0;
-  return vcg_in_stats_pass(y, mean, rstd, g.N, g.Ho * g.Wo, g.Cout, eps, part, ws_bytes - cws, (hipStream_t)stream);
-}
 
-static int dgrad_setup(const ConvGeom& g, ConvP& p, int& bm, int& bn, int& nsplit, int& kt_per) {
-  p.Hc = g.Hl / g.stride; p.Wc = g.Wl / g.stride; p.Mc = g.N * p.Hc * p.Wc;
-  p.NB = g.ups * g.ups * g.Cin;
-  p.fd_hcwc = make_fastdiv((uint32_t)(p.Hc * p.Wc));
-  p.fd_wc = make_fastdiv((uint32_t)p.Wc);
-  // stride s: s * s parity classes, each a GEMM over its own (KH / s) x (KW / s) taps — the planner sees them as batches,
-  // and blockIdx.z = class + s * s * K slice
-  const int s = g.stride;
-  gemm_plan(p.Mc, p.NB, (g.KH * g.KW * g.Cout + BK - 1) / BK, s == 1, bm, bn, nsplit, kt_per, 1, true);
-  if (s > 1 && g.KH % s == 0 && g.KW % s == 0) {
-    // the unsliced plan fills the chip for the large maps (measured: slicing made 64 -> 128 at 128^2 and 128 -> 256 at 64^2
-    // slower); the deep layer (256 -> 512 at 32^2: 256 workgroups) is the one that needs its K cut
-    const long long wgs = ((p.Mc + bm - 1) / bm) * ((p.NB + bn - 1) / bn) * s * s;
-    if (wgs < 384)
-      gemm_plan(p.Mc, p.NB, ((g.KH / s) * (g.KW / s) * g.Cout + BK - 1) / BK, true, bm, bn, nsplit, kt_per, s * s, true);
-  }
-  return 0;
-}
-
-// does the forward / the data gradient at this geometry read the fp32 Wf block?  (mirrors conv_fwd_impl and vcg_conv_dgrad)
-static bool fwd_reads_wf(const ConvGeom& g) {
-  if (vcg_thin_fold_ok(g)) return false;
-  if (vcg_thin_fwd_ok(g) || vcg_thinin_fwd_ok(g)) return true;
-  if (vcg_wino_fwd_ok(g) || fwd_slab_ok(g)) return false;
-  int bm, bn, nsplit, kt_per;
-  fwd_plan(g, bm, bn, nsplit, kt_per);
-  return !(bm == 128 && bn >= 64 && wft_wanted(g));
-}
-static bool dgrad_reads_wf(const ConvGeom& g) {
-  if (g.Hl % g.stride || g.Wl % g.stride) return true;
-  if (vcg_thin_fold_dgrad_ok(g)) return false;
-  if (vcg_thin_dgrad_ok(g)) return true;
-  if (vcg_wino_dgrad_ok(g) || dgrad_slab_ok(g)) return false;
-  ConvP p; fill_params(g, p);
-  int bm, bn, nsplit, kt_per;
-  dgrad_setup(g, p, bm, bn, nsplit, kt_per);
-  return !(bm == 128 && bn >= 64 && wfd_wanted(g));          // planes; everything else (no planes, 32-column, fp32) reads Wf
-}
+// does the forward or the data gradient at this geometry read the fp32 Wf block?
 extern "C" int vcg_conv_reads_wf(const int32_t* cd) {
   ConvGeom g;
   if (vcg_conv_geom(cd, &g, "vcg_conv_reads_wf")) return 1;
-  return (fwd_reads_wf(g) || dgrad_reads_wf(g)) ? 1 : 0;
+  return (plan_fwd(g).reads_wf || plan_dgrad(g).reads_wf) ? 1 : 0;
 }
 
 extern "C" size_t vcg_conv_dgrad_workspace(const int32_t* cd) {
   ConvGeom g;
   if (vcg_conv_geom(cd, &g, "vcg_conv_dgrad_workspace")) return 0;
-  if (g.Hl % g.stride || g.Wl % g.stride) return 0;
-  if (vcg_thin_fold_dgrad_ok(g)) return vcg_thin_fold_dgrad_workspace(g);
-  if (vcg_thin_dgrad_ok(g)) return vcg_thin_dgrad_workspace(g);
-  if (vcg_wino_dgrad_ok(g)) return vcg_wino_dgrad_workspace(g);
-  if (dgrad_slab_ok(g)) return vcg_slab_dgrad_workspace(g);
-  ConvP p; fill_params(g, p);
-  int bm, bn, nsplit, kt_per;
-  dgrad_setup(g, p, bm, bn, nsplit, kt_per);
-  return nsplit > 1 ? (size_t)nsplit * g.N * g.H * g.W * g.Cin * sizeof(float) + 256 : 0;
+  return plan_dgrad(g).ws;
+}
+
+static KernelRef dgrad_kernel(const DgradPlan& pl) {
+  const int bm = pl.t.bm, bn = pl.t.bn;
+  if (pl.path == DGRAD_SPLIT_PLANES && bn == 128) return {k_conv_dgrad_split<128, 2>, "k_conv_dgrad_split<128, 2>"};
+  if (pl.path == DGRAD_SPLIT_PLANES) return {k_conv_dgrad_split<64, 2>, "k_conv_dgrad_split<64, 2>"};
+  if (pl.path == DGRAD_SPLIT32) return {k_conv_dgrad_split<32, 1>, "k_conv_dgrad_split<32, 1>"};
+  if (pl.path == DGRAD_SPLIT64_NOPLANES) return {k_conv_dgrad_split<64, 2, false>, "k_conv_dgrad_split<64, 2>"};
+  const char* const name = "k_conv_dgrad<fp32 MFMA>";
+  if (bn == 32) return {k_conv_dgrad<128, 32, 1>, name};
+  if (bm == 128 && bn == 128) return {k_conv_dgrad<128, 128>, name};
+  if (bm == 128 && bn == 64) return {k_conv_dgrad<128, 64>, name};
+  if (bm == 64 && bn == 128) return {k_conv_dgrad<64, 128>, name};
+  return {k_conv_dgrad<64, 64>, name};
+}
+// the ConvP of a tile launch of the data gradient: blockIdx.z = parity class + s * s * K slice
+static void dgrad_setup(const ConvGeom& g, const DgradPlan& pl, void* ws, ConvP& p) {
+  p.Hc = g.Hl / g.stride; p.Wc = g.Wl / g.stride; p.Mc = g.N * p.Hc * p.Wc;
+  p.NB = g.ups * g.ups * g.Cin;
+  p.fd_hcwc = make_fastdiv((uint32_t)(p.Hc * p.Wc));
+  p.fd_wc = make_fastdiv((uint32_t)p.Wc);
+  auto dbl = [&](int L) { int lo = 1 > L - 1 - g.pad ? 1 : L - 1 - g.pad, hi = g.pad < L - 2 ? g.pad : L - 2; return lo <= hi; };
+  p.dbl_mirror = g.reflect && (dbl(g.Hl) || dbl(g.Wl));
+  if (pl.t.nsplit > 1) { p.ksplit = pl.t.nsplit; p.kt_per = pl.t.kt_per; p.slab = (float*)ws; }
 }
 
 extern "C" int vcg_conv_dgrad(const float* dy, const float* wf, float* dx, const int32_t* cd, void* ws,
@@ -2436,56 +2457,35 @@ extern "C" int vcg_conv_dgrad(const float* dy, const float* wf, float* dx, const
   ConvGeom g;
   if (vcg_conv_geom(cd, &g, "vcg_conv_dgrad")) return -1;
   VCG_CHECK_ARG(dy && wf && dx, "vcg_conv_dgrad: null pointer");
-  VCG_CHECK_ARG(g.Hl % g.stride == 0 && g.Wl % g.stride == 0, "vcg_conv_dgrad: input %dx%d not divisible by stride", g.Hl, g.Wl);
+  const DgradPlan pl = plan_dgrad(g);
+  VCG_CHECK_ARG(pl.path != DGRAD_UNSUPPORTED, "vcg_conv_dgrad: input %dx%d not divisible by stride", g.Hl, g.Wl);
   VCG_CHECK_ARG(g.stride == 1 || g.ups == 1, "vcg_conv_dgrad: stride 2 with ups 2 unsupported");
-  if (vcg_thin_fold_dgrad_ok(g)) return vcg_thin_fold_dgrad(g, dy, wf + wkd_offset(g), vcg_pack_amax(g, wf), dx, ws, ws_bytes, (hipStream_t)stream, dy_handle);
-  if (vcg_thin_dgrad_ok(g)) return vcg_thin_dgrad(g, dy, wf, dx, ws, ws_bytes, (hipStream_t)stream);
-  if (vcg_wino_dgrad_ok(g))
-    return vcg_wino_dgrad(g, dy, wf + wf_floats(g) + wino_u_floats(g), vcg_pack_amax(g, wf), dx, ws, ws_bytes, (hipStream_t)stream, dy_handle);
-  if (dgrad_slab_ok(g))
-    return vcg_slab_dgrad(g, dy, wf + wfd_offset(g), wfd_floats(g) * 4, vcg_pack_amax(g, wf), dx, ws, ws_bytes, (hipStream_t)stream, dy_handle);
+  const PackLayout L = pack_layout(g);
+  const void* const w_amax = wf + L.hdr;
+  hipStream_t st = (hipStream_t)stream;
+  if (pl.path == DGRAD_THIN_FOLD) return vcg_thin_fold_dgrad(g, dy, wf + L.wkd, w_amax, dx, ws, ws_bytes, st, dy_handle);
+  if (pl.path == DGRAD_THIN) return vcg_thin_dgrad(g, dy, wf, dx, ws, ws_bytes, st);
+  if (pl.path == DGRAD_WINO) return vcg_wino_dgrad(g, dy, wf + L.ud, w_amax, dx, ws, ws_bytes, st, dy_handle);
+  if (pl.path == DGRAD_SLAB) return vcg_slab_dgrad(g, dy, wf + L.wfd, (L.hdr - L.wfd) * 4, w_amax, dx, ws, ws_bytes, st, dy_handle);
   ConvP p; fill_params(g, p);
   p.a = dy; p.b = wf; p.out = dx;
-  {
-    const unsigned long long ab = (unsigned long long)g.M * g.Cout * 4, bb = (unsigned long long)g.K * g.Cout * 4;
-    VCG_CHECK_ARG(ab < (1ull << 31) && bb < (1ull << 31), "vcg_conv_dgrad: tensor extents must stay below 2 GiB");
-    p.a_bytes = (uint32_t)ab; p.b_bytes = (uint32_t)bb;
+  if (set_extents(p, (unsigned long long)g.M * g.Cout * 4, (unsigned long long)g.K * g.Cout * 4,
+                  "vcg_conv_dgrad: tensor extents must stay below 2 GiB")) return -1;
+  const int nsplit = pl.t.nsplit;
+  if (nsplit > 1) VCG_CHECK_ARG(ws && ws_bytes >= pl.ws, "vcg_conv_dgrad: workspace too small (%zu)", ws_bytes);
+  dgrad_setup(g, pl, ws, p);
+  if (pl.path == DGRAD_SPLIT_PLANES) { p.b = wf + L.wfd; p.b_bytes = (uint32_t)((L.hdr - L.wfd) * 4); }
+  if (pl.path != DGRAD_FP32) {                              // fp16 x 2 kernels: the operands' largest magnitudes (vcg_common.h)
+    // the kernel ADDS the sources that reflect padding folds onto a pixel before it splits the sum: up to 4 of them (9 on maps
+    // so small that a pixel has mirrors on both sides) — the operand is bounded by 2^4 x dy's largest magnitude, not by it
+    if (vcg_operand_amax(dy, (size_t)g.M * g.Cout, dy_handle, g.reflect ? 4 : 0, st, &p.amax_a)) return -2;
+    p.amax_b = vcg_amax_stored(w_amax);
   }
   {
-    auto dbl = [&](int L) { int lo = 1 > L - 1 - g.pad ? 1 : L - 1 - g.pad, hi = g.pad < L - 2 ? g.pad : L - 2; return lo <= hi; };
-    p.dbl_mirror = g.reflect && (dbl(g.Hl) || dbl(g.Wl));
-  }
-  int bm, bn, nsplit, kt_per;
-  dgrad_setup(g, p, bm, bn, nsplit, kt_per);
-  if (nsplit > 1) {
-    VCG_CHECK_ARG(ws && ws_bytes >= vcg_conv_dgrad_workspace(cd), "vcg_conv_dgrad: workspace too small (%zu)", ws_bytes);
-    p.ksplit = nsplit; p.kt_per = kt_per; p.slab = (float*)ws;
-  }
-  dim3 grid((p.Mc + bm - 1) / bm, (p.NB + bn - 1) / bn, nsplit * g.stride * g.stride);
-  hipStream_t st = (hipStream_t)stream;
-  {
-    const double gemm_flops = 2.0 * g.M * (double)g.K * g.Cout;   // stride 2: the parity classes together visit every tap once
-    const bool planes = bm == 128 && bn >= 64 && wfd_wanted(g);       // weight rows from the pre-split WFD planes of the pack
-    if (planes) { p.b = wf + wfd_offset(g); p.b_bytes = (uint32_t)(wfd_floats(g) * 4); }
-    // layers without planes (the 4-channel dy of the 7x7 head: K = (tap, co) is not a multiple of 32 per tap) still run on the
-    // 16-bit pipe when their tile is 128 x 64: the weight rows are split in the kernel from Wf
-    const bool nopl64 = !planes && bm == 128 && bn == 64 && g.Cout % 4 == 0;
-    const bool split = planes || bn == 32 || nopl64;
-    if (split) {                                            // fp16 x 2 kernels: the operands' largest magnitudes (vcg_common.h)
-      // the kernel ADDS the sources that reflect padding folds onto a pixel before it splits the sum: up to 4 of them (9 on maps
-      // so small that a pixel has mirrors on both sides) — the operand is bounded by 2^4 x dy's largest magnitude, not by it
-      if (vcg_operand_amax(dy, (size_t)g.M * g.Cout, dy_handle, g.reflect ? 4 : 0, st, &p.amax_a)) return -2;
-      p.amax_b = vcg_amax_stored(vcg_pack_amax(g, wf));
-    }
-    VcgProfScope prof(!split ? "k_conv_dgrad<fp32 MFMA>" : bn == 128 ? "k_conv_dgrad_split<128, 2>" : bn == 64 ? "k_conv_dgrad_split<64, 2>"
-                                                                                                             : "k_conv_dgrad_split<32, 1>",
-                      gemm_flops, st);
-    if (planes) {                                           // split-operand kernel
-      if (bn == 128) hipLaunchKernelGGL((k_conv_dgrad_split<128, 2>), grid, dim3(256), 0, st, p);
-      else hipLaunchKernelGGL((k_conv_dgrad_split<64, 2>), grid, dim3(256), 0, st, p);
-    } else if (bn == 32) hipLaunchKernelGGL((k_conv_dgrad_split<32, 1>), grid, dim3(256), 0, st, p);
-    else if (nopl64) hipLaunchKernelGGL((k_conv_dgrad_split<64, 2, false>), grid, dim3(256), 0, st, p);
-    else DISPATCH_DGRAD(bm, bn, grid, st, p);
+    const KernelRef k = dgrad_kernel(pl);
+    dim3 grid((p.Mc + pl.t.bm - 1) / pl.t.bm, (p.NB + pl.t.bn - 1) / pl.t.bn, nsplit * g.stride * g.stride);
+    VcgProfScope prof(k.name, 2.0 * g.M * (double)g.K * g.Cout, st);   // stride 2: the parity classes together visit every tap once
+    hipLaunchKernelGGL(k.fn, grid, dim3(256), 0, st, p);
   }
   if (nsplit > 1)
     hipLaunchKernelGGL(k_splitk_finish, dim3(ew_grid((size_t)g.N * g.H * g.W * g.Cin / 4)), dim3(256), 0, st,
@@ -2540,6 +2540,24 @@ static WgradPlan wgrad_plan(const ConvGeom& g, int batches = 1) {
   return best_p;
 }
 
+// one stream-K launch of the weight-gradient kernel: the plan's share of ConvP (a batched caller sets sk_ntr_pb itself) ...
+static void stream_k_setup(const WgradPlan& wp, ConvP& p) {
+  p.ktiles_total = wp.total; p.sk_len = wp.len; p.sk_units = wp.ntr * wp.ntn * wp.total; p.sk_ntn = wp.ntn;
+  p.sk_bm_shift = wp.bm == 256 ? 8 : wp.bm == 128 ? 7 : 6; p.sk_bn_shift = wp.bn == 128 ? 7 : 6;
+  p.fd_sklen = make_fastdiv((uint32_t)wp.len);
+}
+// ... and the kernel of its tile (128 rows: the split-operand kernels; 256: the lockstep workgroup of the diagnostic build)
+static void launch_stream_k(const WgradPlan& wp, const ConvP& p, double flops, hipStream_t st) {
+  const int bm = wp.bm, bn = wp.bn;
+  const KernelRef k = bm == 128 && bn == 128  ? KernelRef{k_conv_wgrad_split<128>, "k_conv_wgrad_split<128>"}
+                      : bm == 128 && bn == 64 ? KernelRef{k_conv_wgrad_split<64>, "k_conv_wgrad_split<64>"}
+                      : bm == 64 && bn == 128 ? KernelRef{k_conv_wgrad<64, 128>, "k_conv_wgrad<fp32 MFMA>"}
+                      : bm == 64              ? KernelRef{k_conv_wgrad<64, 64>, "k_conv_wgrad<fp32 MFMA>"}
+                                              : KernelRef{k_conv_wgrad<256, 128, 512>, "k_conv_wgrad<fp32 MFMA>"};
+  VcgProfScope prof(k.name, flops, st);
+  hipLaunchKernelGGL(k.fn, dim3(wp.grid), dim3(bm == 256 ? 512 : 256), 0, st, p);
+}
+
 static const int kMaxDirectSlabs = 24;
 
 // bias-gradient column sums: TC channel quads per block, ~1024 blocks in flight
@@ -2557,30 +2575,27 @@ static void colsum_plan(const ConvGeom& g, int& tc, int& cgroups, int& rows, int
   nchunk = (g.M + rows - 1) / rows;
 }
 
-static bool wgrad_swapped_ok(const ConvGeom& g);
-static ConvGeom swapped_geom(const ConvGeom& g);
-
 // Winograd weight gradient core (conv_wino.hip provides V = B^T x B and dM = A dy A^T): the 16 reductions
 // dU[xi] = V[xi]^T dM[xi] over the T tiles run as ONE stream-K launch of the wgrad kernel (a 1x1 "convolution" whose
 // row tiles enumerate (xi, k-tile)), then k_wino_wgrad_reduce transforms back and accumulates into the OIHW gradient.
-static ConvGeom wino_gemm_geom(const ConvGeom& g, int T) {
-  ConvGeom q = {};
-  q.N = 1; q.H = 1; q.W = T; q.Cin = g.ups * g.ups * g.Cin; q.Cout = g.Cout; q.KH = q.KW = 1; q.stride = 1; q.pad = 0;
-  q.reflect = 0; q.ups = 1; q.act = VCG_ACT_NONE; q.cin_log = q.Cin; q.cout_log = g.Cout;
-  q.Hl = 1; q.Wl = T; q.Ho = 1; q.Wo = T; q.M = T; q.K = q.Cin; q.taps = 1;
-  return q;
+static ConvGeom wino_gemm_geom(const ConvGeom& g, int T) { return gemm_geom(T, g.ups * g.ups * g.Cin, g.Cout); }
+static int wino_wgrad_reduce(const ConvGeom& g, const ConvP& p, const float* dU, float* gw_oihw, hipStream_t st) {
+  hipLaunchKernelGGL(k_wino_wgrad_reduce, dim3(g.Cout / 64, (g.Cin + 7) / 8, g.ups * g.ups), dim3(256), 0, st, dU, gw_oihw, p, g.Cin,
+                     g.ups, g.cin_log, g.cout_log);
+  VCG_LAUNCH_CHECK("vcg_conv_wgrad(winograd reduce)");
+  return 0;
 }
+static size_t wino_core_bytes(const ConvGeom& q, const WgradPlan& wp) { return (size_t)wp.parts * 16 * q.K * q.Cout * sizeof(float) + 256; }
 size_t vcg_wino_wgrad_core_workspace(const ConvGeom& g, int T) {
   const ConvGeom q = wino_gemm_geom(g, T);
-  const WgradPlan wp = wgrad_plan(q, 16);
-  return (size_t)wp.parts * 16 * q.K * q.Cout * sizeof(float) + 256;
+  return wino_core_bytes(q, wgrad_plan(q, 16));
 }
 int vcg_wino_wgrad_core(const ConvGeom& g, const float* V, const float* dM, int T, float* gw_oihw, void* ws, size_t ws_bytes,
                         hipStream_t st, const VcgAmax& amax_v, const VcgAmax& amax_dm) {
   const ConvGeom q = wino_gemm_geom(g, T);
   const WgradPlan wp = wgrad_plan(q, 16);
   VCG_CHECK_ARG(wp.grid > 0, "vcg_conv_wgrad: no launch plan for the Winograd path");
-  VCG_CHECK_ARG(ws_bytes >= vcg_wino_wgrad_core_workspace(g, T), "vcg_conv_wgrad: Winograd slab workspace too small");
+  VCG_CHECK_ARG(ws_bytes >= wino_core_bytes(q, wp), "vcg_conv_wgrad: Winograd slab workspace too small");
   ConvP p; fill_params(q, p);
   p.a = V; p.b = dM; p.out = (float*)ws;
   p.amax_a = amax_v; p.amax_b = amax_dm;
@@ -2588,24 +2603,11 @@ int vcg_wino_wgrad_core(const ConvGeom& g, const float* V, const float* dM, int 
   VCG_CHECK_ARG(wp.bm == 128 && q.K % 32 == 0, "vcg_conv_wgrad: pre-split V needs the split-operand tile");
   p.a_bytes = (uint32_t)((size_t)T * q.K * 4); p.b_bytes = (uint32_t)((size_t)T * q.Cout * 4);
   p.nbatch = 16; p.a_bstride = (uint32_t)((size_t)T * q.K); p.b_bstride = (uint32_t)((size_t)T * q.Cout);
-  p.ktiles_total = wp.total; p.sk_len = wp.len; p.sk_units = wp.ntr * wp.ntn * wp.total; p.sk_ntn = wp.ntn;
-  p.sk_bm_shift = wp.bm == 256 ? 8 : wp.bm == 128 ? 7 : 6; p.sk_bn_shift = wp.bn == 128 ? 7 : 6;
+  stream_k_setup(wp, p);
   p.sk_ntr_pb = wp.ntr / 16;
-  p.fd_sklen = make_fastdiv((uint32_t)wp.len);
-  dim3 grid(wp.grid);
-  {
-    VcgProfScope prof(wp.bm == 128 ? (wp.bn == 128 ? "k_conv_wgrad_split<128>" : "k_conv_wgrad_split<64>") : "k_conv_wgrad<fp32 MFMA>",
-                      2.0 * 16 * (double)T * q.K * q.Cout, st);
-    if (wp.bm == 128 && wp.bn == 128) hipLaunchKernelGGL(k_conv_wgrad_split<128>, grid, dim3(256), 0, st, p);        // split-operand
-    else if (wp.bm == 128 && wp.bn == 64) hipLaunchKernelGGL(k_conv_wgrad_split<64>, grid, dim3(256), 0, st, p);
-    else if (wp.bm == 64 && wp.bn == 128) hipLaunchKernelGGL((k_conv_wgrad<64, 128>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_conv_wgrad<64, 64>), grid, dim3(256), 0, st, p);
-  }
+  launch_stream_k(wp, p, 2.0 * 16 * (double)T * q.K * q.Cout, st);
   VCG_LAUNCH_CHECK("vcg_conv_wgrad(winograd gemm)");
-  hipLaunchKernelGGL(k_wino_wgrad_reduce, dim3(g.Cout / 64, (g.Cin + 7) / 8, g.ups * g.ups), dim3(256), 0, st,
-                     (const float*)ws, gw_oihw, p, g.Cin, g.ups, g.cin_log, g.cout_log);
-  VCG_LAUNCH_CHECK("vcg_conv_wgrad(winograd reduce)");
-  return 0;
+  return wino_wgrad_reduce(g, p, (const float*)ws, gw_oihw, st);
 }
 
 // the back-transform of a dU that is already whole (vcg_wino_wgrad's transposed-operand GEMM): k_wino_wgrad_reduce over one part
@@ -2615,27 +2617,7 @@ int vcg_wino_wgrad_reduce_one(const ConvGeom& g, const float* dU, float* gw_oihw
   p.nbatch = 16;
   p.ktiles_total = 1; p.sk_len = 1; p.sk_ntn = 1; p.sk_bm_shift = 30; p.sk_bn_shift = 30;      // sk_parts() == 1 everywhere
   p.fd_sklen = make_fastdiv(1u);
-  hipLaunchKernelGGL(k_wino_wgrad_reduce, dim3(g.Cout / 64, (g.Cin + 7) / 8, g.ups * g.ups), dim3(256), 0, st, dU, gw_oihw, p, g.Cin,
-                     g.ups, g.cin_log, g.cout_log);
-  VCG_LAUNCH_CHECK("vcg_conv_wgrad(winograd reduce)");
-  return 0;
-}
-
-extern "C" size_t vcg_conv_wgrad_workspace(const int32_t* cd) {
-  ConvGeom g;
-  if (vcg_conv_geom(cd, &g, "vcg_conv_wgrad_workspace")) return 0;
-  const ConvGeom gorig = g;
-  int tc, cgroups, rows, nchunk;
-  colsum_plan(gorig, tc, cgroups, rows, nchunk);
-  size_t cols = (size_t)nchunk * gorig.Cout * sizeof(float);
-  if (vcg_wino_wgrad_ok(g)) return ((vcg_wino_wgrad_workspace(g) + 255) / 256) * 256 + cols + 1024;
-  if (wgrad_ring_ok(g)) return ((vcg_ring_wgrad_workspace(g) + 255) / 256) * 256 + cols + 1024;
-  if (wgrad_swapped_ok(g)) g = swapped_geom(g);
-  const WgradPlan wp = wgrad_plan(g);
-  const int nsplit = wp.parts;
-  size_t slabs = (size_t)nsplit * g.K * g.Cout * sizeof(float);
-  size_t groups = (size_t)16 * g.K * g.Cout * sizeof(float);     // k_slab_sum output (used when nsplit > 8)
-  return slabs + groups + cols + 1024;
+  return wino_wgrad_reduce(g, p, dU, gw_oihw, st);
 }
 
 // Thin Cout (the decoder head, 64 -> 3): dW[(tap,c)][co<4] as an MFMA GEMM wastes 15/16 of the tile.  With
@@ -2651,6 +2633,54 @@ static ConvGeom swapped_geom(const ConvGeom& g) {
   return s;
 }
 
+enum WgradPath { WGRAD_WINO, WGRAD_RING, WGRAD_SWAPPED, WGRAD_STREAM_K };
+enum WgradReduce { WRED_SCATTER, WRED_SCATTER_SWAPPED, WRED_REDUCE };
+// Workspace, every section on a 256-byte boundary: [main: the Winograd / ring kernels' own workspace, or the stream-K part
+// slabs][the <= 16 group slabs of k_slab_sum][bias column-sum partials]
+struct WgradWs { size_t slabs_off, slabs_bytes, groups_off, colsum_off, total; };
+struct WgradRoute {
+  WgradPath path;
+  ConvGeom g;              // the GEMM's geometry: the layer's, or with the roles swapped
+  WgradPlan wp;            // SWAPPED, STREAM_K
+  bool slab_sum;           // more than kMaxDirectSlabs parts: k_slab_sum pre-sums them into group slabs
+  WgradReduce reduce;
+  WgradWs ws;
+};
+static WgradRoute plan_wgrad(const ConvGeom& g) {
+  WgradRoute r = {};
+  r.g = g;
+  int tc, cgroups, rows, nchunk;
+  colsum_plan(g, tc, cgroups, rows, nchunk);
+  const size_t cols = (size_t)nchunk * g.Cout * sizeof(float);
+  size_t groups = 0;
+  if (vcg_wino_wgrad_ok(g)) { r.path = WGRAD_WINO; r.ws.slabs_bytes = vcg_wino_wgrad_workspace(g); }
+  else if (vcg_ring_wgrad_ok(g)) { r.path = WGRAD_RING; r.ws.slabs_bytes = vcg_ring_wgrad_workspace(g); }
+  else {
+    const bool swapped = wgrad_swapped_ok(g);
+    r.path = swapped ? WGRAD_SWAPPED : WGRAD_STREAM_K;
+    if (swapped) r.g = swapped_geom(g);
+    r.wp = wgrad_plan(r.g);
+    const size_t totalw = (size_t)r.g.K * r.g.Cout;
+    r.ws.slabs_bytes = (size_t)r.wp.parts * totalw * sizeof(float);
+    groups = (size_t)16 * totalw * sizeof(float);
+    r.slab_sum = r.wp.parts > kMaxDirectSlabs;
+    const size_t lds = (size_t)r.g.taps * 8 * 33 * sizeof(float);      // k_wgrad_reduce's tile
+    r.reduce = swapped ? WRED_SCATTER_SWAPPED : (totalw < (1u << 20) || lds > 64 * 1024) ? WRED_SCATTER : WRED_REDUCE;
+  }
+  r.ws.groups_off = up256(r.ws.slabs_bytes);
+  r.ws.colsum_off = r.ws.groups_off + up256(groups);
+  r.ws.total = r.ws.colsum_off + cols + 1024;
+  // the stream-K size counts its part slabs unrounded, as it always has: their rounding comes out of the 1024 of slack
+  if (groups) r.ws.total -= r.ws.groups_off - r.ws.slabs_bytes;
+  return r;
+}
+
+extern "C" size_t vcg_conv_wgrad_workspace(const int32_t* cd) {
+  ConvGeom g;
+  if (vcg_conv_geom(cd, &g, "vcg_conv_wgrad_workspace")) return 0;
+  return plan_wgrad(g).ws.total;
+}
+
 static int launch_colsum(const ConvGeom& gorig, const float* dy, float* gbias, float* part, hipStream_t st) {
   int tc, cgroups, rows, nchunk;
   colsum_plan(gorig, tc, cgroups, rows, nchunk);
@@ -2661,100 +2691,67 @@ static int launch_colsum(const ConvGeom& gorig, const float* dy, float* gbias, f
   return 0;
 }
 
-extern "C" int vcg_conv_wgrad_saved(const float* x, const float* dy, float* gw_oihw, float* gbias, const float* saved,
-                                    const int32_t* cd, void* ws, size_t ws_bytes, void* stream);
-extern "C" int vcg_conv_wgrad(const float* x, const float* dy, float* gw_oihw, float* gbias,
-                              const int32_t* cd, void* ws, size_t ws_bytes, void* stream) {
-  return vcg_conv_wgrad_saved(x, dy, gw_oihw, gbias, nullptr, cd, ws, ws_bytes, stream);
-}
 // `saved`: what vcg_conv_fwd_in left for this very (x, cd) in its `saved` buffer (vcg_conv_saved_floats), or null
 extern "C" int vcg_conv_wgrad_saved(const float* x, const float* dy, float* gw_oihw, float* gbias, const float* saved,
                                     const int32_t* cd, void* ws, size_t ws_bytes, void* stream) {
   const uint64_t x_handle = vcg_take_hint_x(), dy_handle = vcg_take_hint_dy();      // vcg_amax_hint
-  ConvGeom g;
-  if (vcg_conv_geom(cd, &g, "vcg_conv_wgrad")) return -1;
+  ConvGeom gorig;
+  if (vcg_conv_geom(cd, &gorig, "vcg_conv_wgrad")) return -1;
   VCG_CHECK_ARG(x && dy && gw_oihw && ws, "vcg_conv_wgrad: null pointer");
-  size_t need = vcg_conv_wgrad_workspace(cd);
-  VCG_CHECK_ARG(ws_bytes >= need, "vcg_conv_wgrad: workspace %zu < %zu", ws_bytes, need);
-  if (vcg_wino_wgrad_ok(g)) {
-    const size_t wbytes = vcg_wino_wgrad_workspace(g);
-    if (vcg_wino_wgrad(g, x, dy, gw_oihw, ws, wbytes, (hipStream_t)stream, saved, x_handle, dy_handle)) return -2;
-    if (gbias) return launch_colsum(g, dy, gbias, (float*)((char*)ws + ((wbytes + 255) / 256) * 256), (hipStream_t)stream);
-    return 0;
-  }
-  if (wgrad_ring_ok(g)) {
-    const size_t rbytes = vcg_ring_wgrad_workspace(g);
-    if (vcg_ring_wgrad(g, x, dy, gw_oihw, ws, rbytes, (hipStream_t)stream, x_handle, dy_handle)) return -2;
-    if (gbias) return launch_colsum(g, dy, gbias, (float*)((char*)ws + ((rbytes + 255) / 256) * 256), (hipStream_t)stream);
-    return 0;
-  }
-  const bool swapped = wgrad_swapped_ok(g);
-  const ConvGeom gorig = g;
-  if (swapped) g = swapped_geom(g);
-  ConvP p; fill_params(g, p);
-  const WgradPlan wp = wgrad_plan(g);
-  const int bm = wp.bm, bn = wp.bn, nsplit = wp.parts;
-  p.a = x; p.b = dy; p.out = (float*)ws;
-  if (swapped) { p.a = dy; p.b = x; p.adjoint = 1; p.src_pitch = 4; }
-  {
-    // a: the gathered side (x; dy in swapped mode), b: the plain [K' pixel][Cout] side
-    const unsigned long long ab = swapped ? (unsigned long long)gorig.M * 4 * 4 : (unsigned long long)g.N * g.H * g.W * g.Cin * 4;
-    const unsigned long long bb = (unsigned long long)g.M * g.Cout * 4;
-    VCG_CHECK_ARG(ab < (1ull << 31) && bb < (1ull << 31), "vcg_conv_wgrad: tensor extents must stay below 2 GiB");
-    p.a_bytes = (uint32_t)ab; p.b_bytes = (uint32_t)bb;
-  }
-  p.ktiles_total = wp.total; p.sk_len = wp.len; p.sk_units = wp.ntr * wp.ntn * wp.total; p.sk_ntn = wp.ntn;
-  p.sk_bm_shift = bm == 256 ? 8 : bm == 128 ? 7 : 6; p.sk_bn_shift = bn == 128 ? 7 : 6;
-  p.fd_sklen = make_fastdiv((uint32_t)wp.len);
-  dim3 grid(wp.grid);
+  const WgradRoute r = plan_wgrad(gorig);
+  VCG_CHECK_ARG(ws_bytes >= r.ws.total, "vcg_conv_wgrad: workspace %zu < %zu", ws_bytes, r.ws.total);
   hipStream_t st = (hipStream_t)stream;
-  if (bm == 128) {                                          // fp16 x 2 kernel: both operands are activations, scaled by their own amax
+  float* const colsum = (float*)((char*)ws + r.ws.colsum_off);
+  if (r.path == WGRAD_WINO || r.path == WGRAD_RING) {
+    if (r.path == WGRAD_WINO ? vcg_wino_wgrad(gorig, x, dy, gw_oihw, ws, r.ws.slabs_bytes, st, saved, x_handle, dy_handle)
+                             : vcg_ring_wgrad(gorig, x, dy, gw_oihw, ws, r.ws.slabs_bytes, st, x_handle, dy_handle))
+      return -2;
+    return gbias ? launch_colsum(gorig, dy, gbias, colsum, st) : 0;
+  }
+  const bool swapped = r.path == WGRAD_SWAPPED;
+  const ConvGeom& g = r.g;
+  const WgradPlan& wp = r.wp;
+  ConvP p; fill_params(g, p);
+  p.a = x; p.b = dy; p.out = (float*)((char*)ws + r.ws.slabs_off);
+  if (swapped) { p.a = dy; p.b = x; p.adjoint = 1; p.src_pitch = 4; }
+  // a: the gathered side (x; dy in swapped mode), b: the plain [K' pixel][Cout] side
+  if (set_extents(p, swapped ? (unsigned long long)gorig.M * 4 * 4 : (unsigned long long)g.N * g.H * g.W * g.Cin * 4,
+                  (unsigned long long)g.M * g.Cout * 4, "vcg_conv_wgrad: tensor extents must stay below 2 GiB")) return -1;
+  stream_k_setup(wp, p);
+  if (wp.bm == 128) {                                       // fp16 x 2 kernel: both operands are activations, scaled by their own amax
     // swapped roles (a = dy, b = x): the rows are gathered from dy through the adjoint of the padding, i.e. as sums of up to 4 (9) sources
     if (vcg_operand_amax(p.a, (size_t)p.a_bytes / 4, swapped ? dy_handle : x_handle, (swapped && gorig.reflect) ? 4 : 0, st, &p.amax_a) ||
         vcg_operand_amax(p.b, (size_t)p.b_bytes / 4, swapped ? x_handle : dy_handle, 0, st, &p.amax_b))
       return -2;
   }
-  {
-    VcgProfScope prof(bm == 128 ? (bn == 128 ? "k_conv_wgrad_split<128>" : "k_conv_wgrad_split<64>") : "k_conv_wgrad<fp32 MFMA>",
-                      2.0 * g.M * (double)g.K * g.Cout, st);
-    if (bm == 256) hipLaunchKernelGGL((k_conv_wgrad<256, 128, 512>), grid, dim3(512), 0, st, p);
-    else if (bm == 128 && bn == 128) hipLaunchKernelGGL(k_conv_wgrad_split<128>, grid, dim3(256), 0, st, p);     // split-operand
-    else if (bm == 128 && bn == 64) hipLaunchKernelGGL(k_conv_wgrad_split<64>, grid, dim3(256), 0, st, p);
-    else if (bm == 64 && bn == 128) hipLaunchKernelGGL((k_conv_wgrad<64, 128>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((k_conv_wgrad<64, 64>), grid, dim3(256), 0, st, p);
-  }
+  launch_stream_k(wp, p, 2.0 * g.M * (double)g.K * g.Cout, st);
   VCG_LAUNCH_CHECK("vcg_conv_wgrad");
   const size_t totalw = (size_t)g.K * g.Cout;
-  const size_t slab_bytes = (((size_t)nsplit * totalw * sizeof(float) + 255) / 256) * 256;
-  const float* src = (const float*)ws;
+  const float* src = p.out;
   int ns = 0;                                  // 0: the final kernels sum each tile's own part count
-  if (nsplit > kMaxDirectSlabs) {              // many thin slabs: parallel pre-sum into <= 16 group slabs
-    float* grp = (float*)((char*)ws + slab_bytes);
-    int per_group = (nsplit + 15) / 16;
-    int G = (nsplit + per_group - 1) / per_group;
+  if (r.slab_sum) {                            // many thin slabs: parallel pre-sum into <= 16 group slabs
+    float* grp = (float*)((char*)ws + r.ws.groups_off);
+    int per_group = (wp.parts + 15) / 16;
+    int G = (wp.parts + per_group - 1) / per_group;
     size_t total4 = totalw / 4;
     int bx = (int)((total4 + 255) / 256); if (bx > 1024) bx = 1024;
     hipLaunchKernelGGL(k_slab_sum, dim3(bx, G), dim3(256), 0, st, src, grp, total4, p, per_group);
     src = grp;
     ns = G;
   }
-  const int T = g.KH * g.KW * g.ups * g.ups;
-  const size_t lds = (size_t)T * 8 * 33 * sizeof(float);
-  if (swapped) {
-    int blocks = (int)((totalw + 255) / 256); if (blocks > 4096) blocks = 4096;
+  int blocks = (int)((totalw + 255) / 256); if (blocks > 4096) blocks = 4096;
+  if (r.reduce == WRED_SCATTER_SWAPPED)
     hipLaunchKernelGGL(k_wgrad_scatter_swapped, dim3(blocks), dim3(256), 0, st, src, gw_oihw, p, g.KH * g.KW, g.Cout, ns,
                        gorig.cin_log, gorig.cout_log);
-  } else if (totalw < (1u << 20) || lds > 64 * 1024) {
-    int blocks = (int)((totalw + 255) / 256); if (blocks > 4096) blocks = 4096;
+  else if (r.reduce == WRED_SCATTER)
     hipLaunchKernelGGL(k_wgrad_scatter, dim3(blocks), dim3(256), 0, st, src, gw_oihw, p, ns, g.cin_log, g.cout_log);
-  } else {
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3((g.Cout + 31) / 32, (g.Cin + 7) / 8), dim3(256), lds, st, src, gw_oihw, p,
-                       ns, g.cin_log, g.cout_log);
-  }
+  else
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3((g.Cout + 31) / 32, (g.Cin + 7) / 8), dim3(256), (size_t)g.taps * 8 * 33 * sizeof(float),
+                       st, src, gw_oihw, p, ns, g.cin_log, g.cout_log);
   VCG_LAUNCH_CHECK("vcg_conv_wgrad(reduce)");
-  if (gbias) {
-    float* part = (float*)((char*)ws + slab_bytes + (((size_t)16 * totalw * sizeof(float) + 255) / 256) * 256);
-    return launch_colsum(gorig, dy, gbias, part, st);
-  }
-  return 0;
+  return gbias ? launch_colsum(gorig, dy, gbias, colsum, st) : 0;
+}
+extern "C" int vcg_conv_wgrad(const float* x, const float* dy, float* gw_oihw, float* gbias,
+                              const int32_t* cd, void* ws, size_t ws_bytes, void* stream) {
+  return vcg_conv_wgrad_saved(x, dy, gw_oihw, gbias, nullptr, cd, ws, ws_bytes, stream);
 }
