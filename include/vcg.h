@@ -39,8 +39,9 @@ extern "C" {
  *   vcg_amax_last()        handle of the amax of the tensor the last such call on this thread wrote (0: none); reading resets it;
  *   vcg_amax_hint(x, dy)   handles for the x / dy operands of the NEXT vcg_conv_fwd / _fwd_in / _dgrad / _wgrad(_saved) call
  *                          on this thread (0 = unknown: measured); consumed by that call.
- * A handle names device-side state of the library's code object; it stays valid for ~15 000 later library calls on the device
- * (a training step makes ~1 000) and is refused — the tensor is measured — once it is older.  Passing a handle that belongs to
+ * A handle names device-side state of the library's code object; it stays valid for the next 10 239 amax generations on the
+ * device (16384 slots less a margin of 6144, csrc/misc.hip; every library call that measures or publishes an amax takes one, a
+ * training step ~1 500) and is refused — the tensor is measured — from the 10 240th on.  Passing a handle that belongs to
  * another tensor scales that operand wrongly: hand over only what vcg_amax_last returned for exactly that tensor. */
 void vcg_amax_hint(uint64_t x_amax, uint64_t dy_amax);
 uint64_t vcg_amax_last(void);

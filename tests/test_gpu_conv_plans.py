@@ -813,28 +813,68 @@ FP16_FWD = ("split64", "split128", "slab", "wino", "thinin")
 FP16_DGRAD = ("split<128,2>", "split<64,2>", "split<32,1>", "split<64,2,false>", "slab", "wino")
 
 
-@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
-def test_conv_plan_against_float64(case, pkg, device):
-    name, _, opts = case
-    lib, nat = pkg._native.lib(), pkg._native
-    cd = case_desc(case)
-    plan = conv_plan(cd)
-    g, pf, pd, pw = plan["g"], plan["fwd"], plan["dgrad"], plan["wgrad"]
-    N, H, W, Cin, Cout, cin_log, cout_log, act = g["N"], g["H"], g["W"], g["Cin"], g["Cout"], g["cin_log"], g["cout_log"], g["act"]
-    Ho, Wo, k = g["Ho"], g["Wo"], g["KH"]
+TIERS = (0, 0, 9, 16, 19, 23, 30)
+
+
+def tier_exponents(n, step=1):
+    """-T[i] for i < n, T cycling through TIERS (step 1) or through every third entry of it (step 3: another order of the same
+    seven, for the second tensor of a product); index 0 is tier 0 either way, so a dimension of length 1 has tier 0 only and the
+    tensor's largest magnitude stays in tier 0"""
+    return torch.tensor([-float(TIERS[(step * i) % len(TIERS)]) for i in range(n)], dtype=torch.float64)
+
+
+def make_operands(case, kind, device="cuda"):
+    """(x, wt, bias, dy, g0, gb0) of a case: pad channels zero, as every producer leaves them.
+    kind "randn": standard normal draws (the weights at He scale, bias 0.1, the accumulators' prior contents 4).
+    kind "tiers": the same draws times exact powers of two, x[n, :, :, c] by 2^-(Tn[n] + Tc[c]), wt[co] by 2^-Tco[co],
+    dy[n, :, :, co] by 2^-(Tn'[n] + Tco'[co]) with the tiers of tier_exponents: every output image, output channel, dx image and
+    gw[co, ci] is fed by one combination of tiers, most of them 2^-16 ... 2^-60 below the scale the tensor's largest magnitude
+    sets; bias, g0 and gb0 as for randn."""
+    assert kind in ("randn", "tiers")
+    name = case[0]
+    g = geom(case_desc(case))
+    N, H, W, Cin, Cout, cin_log, cout_log, k = g["N"], g["H"], g["W"], g["Cin"], g["Cout"], g["cin_log"], g["cout_log"], g["KH"]
     seed = sum(map(ord, name)) * 7919
-    st = _st()
-    # ---- data: pad channels zero, as every producer leaves them
     x = torch.randn((N, H, W, Cin), generator=_gen(seed, device), device=device)
     x[..., cin_log:] = 0
     wt = torch.randn((cout_log, cin_log * g["ups"] ** 2, k, k), generator=_gen(seed + 1, device), device=device)
     wt *= (2.0 / (g["K"])) ** 0.5
     bias = torch.randn((Cout,), generator=_gen(seed + 2, device), device=device) * 0.1
     bias[cout_log:] = 0
-    dy = torch.randn((N, Ho, Wo, Cout), generator=_gen(seed + 3, device), device=device)
+    dy = torch.randn((N, g["Ho"], g["Wo"], Cout), generator=_gen(seed + 3, device), device=device)
     dy[..., cout_log:] = 0
     g0 = torch.randn(wt.shape, generator=_gen(seed + 4, device), device=device) * 4.0       # what gw holds before the call
     gb0 = torch.randn((cout_log,), generator=_gen(seed + 5, device), device=device) * 4.0
+    if kind == "tiers":
+        def p2(e):
+            return torch.exp2(e).to(device=device, dtype=torch.float32)
+        x *= p2(tier_exponents(N)[:, None, None, None] + tier_exponents(Cin)[None, None, None, :])
+        wt *= p2(tier_exponents(cout_log)[:, None, None, None])
+        dy *= p2(tier_exponents(N, 3)[:, None, None, None] + tier_exponents(Cout, 3)[None, None, None, :])
+    return x, wt, bias, dy, g0, gb0
+
+
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_conv_plan_against_float64(case, pkg, device):
+    run_conv_plan(case, pkg, device, "randn")
+
+
+def run_conv_plan(case, pkg, device, kind):
+    """Everything the module docstring lists, on the operands make_operands(case, kind) builds.  kind "tiers" leaves the
+    vcg_conv_fwd_in_pre options out: that operand is normalised by construction."""
+    name, _, opts = case
+    if kind != "randn":
+        name = f"{name} [{kind}]"
+        opts = tuple(o for o in opts if not o.startswith("pre"))
+    lib, nat = pkg._native.lib(), pkg._native
+    cd = case_desc(case)
+    plan = conv_plan(cd)
+    g, pf, pd, pw = plan["g"], plan["fwd"], plan["dgrad"], plan["wgrad"]
+    N, H, W, Cin, Cout, cin_log, cout_log, act = g["N"], g["H"], g["W"], g["Cin"], g["Cout"], g["cin_log"], g["cout_log"], g["act"]
+    Ho, Wo, k = g["Ho"], g["Wo"], g["KH"]
+    seed = sum(map(ord, case[0])) * 7919
+    st = _st()
+    x, wt, bias, dy, g0, gb0 = make_operands(case, kind, device)
 
     def pack(flags):
         cdp = case_desc(case)

@@ -803,3 +803,52 @@ def test_eps_tickets_keep_the_reference_draw_order(pkg):
             pass
     assert not ops._TICKETS
     ops.manual_seed(0)
+
+
+def test_operand_range_cases_reach_every_fp16_family():
+    """tests/test_gpu_operand_range.py runs tiered operands through one case per fp16 x 2 kernel family, picked by the dispatch mirror
+    (the smallest reduction length that conv_plan maps to the family): the pick must keep covering every member of FP16_FWD and
+    FP16_DGRAD, the thin-fold MFMA kernel, the three Winograd GEMMs and the fp16 weight-gradient branches, one of them from
+    `saved` — a plan change that empties a family fails here, naming it."""
+    from test_gpu_conv_plans import FP16_DGRAD, FP16_FWD
+    from test_gpu_operand_range import TIER_CASES, TIER_REQUIRED, tier_selection
+    for b in FP16_FWD:
+        assert any(r.startswith(f"fwd {b}") for r in TIER_REQUIRED), b
+    for b in FP16_DGRAD:
+        assert f"dgrad {b}" in TIER_REQUIRED, b
+    sel = tier_selection(TIER_CASES)
+    missing = [f for f in TIER_REQUIRED if f not in sel]
+    assert not missing, f"no tiered case reaches: {missing}"
+    full = tier_selection()
+    assert {f: sel[f][0] for f in TIER_REQUIRED} == {f: full[f][0] for f in TIER_REQUIRED}, "not the smallest reduction length"
+
+
+def test_operand_range_bound_rejects_broken_splits():
+    """The inputs and the tolerance of the tiered GPU tests can see what they are for, independently of the kernels: the
+    documented fp16 x 2 arithmetic emulated on a plain GEMM (test_gpu_operand_range.emulate_gemm) with tiered operands, at the
+    smallest and the largest reduction length the tiered cases use.  The faithful emulation stays within the per-element bound
+    c_path U A + F of test_gpu_conv_plans.py; each broken one leaves it on at least one element: fp16 subnormals flushed to zero,
+    the low piece dropped below 2^-17 of amax, and s one binade too small for a Winograd-style operand (bounded by
+    2^shift amax; one element planted at that bound with amax at the top of its binade: the only place an off-by-one shift
+    shows, as an fp16 overflow)."""
+    from test_gpu_operand_range import TIER_REQUIRED, emulate_gemm, gemm_bound, tier_selection, tiered_gemm_operands
+    sel = tier_selection()
+    lengths = [sel[f][0] for f in TIER_REQUIRED]
+    for K in (min(lengths), max(lengths)):
+        A, B = tiered_gemm_operands(112, K, 112, 20261018)
+        ref, tol = A.double() @ B.double(), gemm_bound(A, B)
+
+        def worst(got):
+            r = (got.double() - ref).abs() / tol
+            return torch.where(torch.isnan(r), torch.full_like(r, float("inf")), r).max().item()
+
+        assert worst(emulate_gemm(A, B)) <= 1.0, f"K = {K}: the faithful emulation leaves the bound"
+        for variant in ("flush", "drop_l"):
+            assert worst(emulate_gemm(A, B, variant)) > 1.0, f"K = {K}: the bound does not see '{variant}'"
+        # the Winograd-style operand: A is bounded by 4 amax(source), the source's amax at the top of its binade and one element
+        # of A (tier 0) at the bound, where a 2 x 2 tile of +-amax in the transform's sign pattern puts it
+        src_amax = (2.0 - 2.0 ** -12) * 2.0 ** torch.tensor(A.abs().max().item()).log2().ceil().item()
+        A[0, 0] = 4.0 * src_amax
+        ref, tol = A.double() @ B.double(), gemm_bound(A, B)
+        assert worst(emulate_gemm(A, B, a_shift=2, a_amax=src_amax)) <= 1.0, f"K = {K}: shift 2 leaves the bound"
+        assert worst(emulate_gemm(A, B, a_shift=1, a_amax=src_amax)) > 1.0, f"K = {K}: the bound does not see a shift of 1 for 2"

@@ -124,6 +124,15 @@ __device__ static inline double wave_sum_d(double v) {
 // which on a chip that answers a denser MFMA stream with a lower clock is what moves the wall time (profiles/r03_gemm_fp16x2_probe.txt).
 // Elements more than 2^17 below the tensor's largest magnitude lose relative (not absolute) precision: their error stays 2^-40
 // of that magnitude, below the fp32 rounding of any sum they enter.
+// The floor, exactly: amax / s lies in [2^14, 2^15).  An element with |x / s| >= 2^-2 (within 2^17 of amax at the top of its
+// binade) has h and l both normal fp16 and keeps 22 bits.  Below that l is an fp16 subnormal (steps of 2^-24), below 2^-14 (2^29
+// under amax) h is one too: h + l is then x / s rounded to a multiple of 2^-24, an absolute error of at most 2^-25 s, which is
+// between 2^-40 and 2^-39 of amax, and an element below 2^-25 s becomes 0.  (fp16 subnormals are kept by the conversions and by
+// the MFMA: a flush would raise the floor to 2^-28 of amax.)  A sum of Kred products of two such operands is therefore off by
+// at most Kred (2^-39 amax_a |b| + 2^-39 amax_b |a|), with rounding errors of either sign far less; the tests hold every output
+// element to c_path U sum|a||b| + F, F = 2^-40 * 2 * Kred * amax_a * amax_b (x 16 for the Winograd operands, which are scaled by
+// the bound 4 amax of the transformed tensor), on operands spread over 2^60 (tests/test_gpu_operand_range.py), and
+// tests/test_host_logic.py shows on an emulation of this arithmetic that the bound rejects a flush and a dropped l.
 #define VCG_NP 2                          // pieces per operand
 #define VCG_PBLK (32 * VCG_NP)            // 16-bit elements per (row, 32-k block) of "blocked planes": [piece][32]
 #define VCG_PBYTES (2 * VCG_PBLK)         // 128 bytes
