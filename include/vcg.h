@@ -345,6 +345,30 @@ int vcg_adam_step(float* p, const float* g, float* m, float* v, size_t n,
                   float step_size, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
                   float eps, float bc2_sqrt, float grad_scale, void* stream);
 
+/* Gradient clipping by global norm (new: the reference has none; torch.nn.utils.clip_grad_norm_'s definition) -------------- */
+/* out (device, 16-byte aligned) receives four floats about the n gradients g (16-byte aligned):
+   out[0] = |grad_scale| sqrt(sum g[i]^2), the 2-norm of the gradient vcg_adam_step would see (+inf where it exceeds fp32);
+   out[1] = min(1, max_norm / (norm + 1e-6)), torch's formula and constant, evaluated in double from the unrounded norm and rounded
+            once to fp32;
+   out[2] = 1.0 if any g[i] is NaN or +-Inf, else 0.0 (decided from the elements, not from out[0]: a finite gradient whose norm
+            saturates fp32 gives out[0] = +inf, out[2] = 0 and the correctly rounded tiny coefficient);
+   out[3] = 0.
+   Squares and sums are taken in double.  Workgroup b sums the floats [b GN_CHUNK, (b + 1) GN_CHUNK) of g, GN_CHUNK = 16384, into a
+   slot of its own in ws; a second single-workgroup pass (256 lanes) sums the slots in a fixed order, adds the n % 4 last
+   elements and writes out.  No float atomics; the grid depends on n alone: the same input gives the same bits on every call.
+   max_norm finite and > 0, grad_scale finite.  n == 0 writes norm 0, coefficient 1, flag 0.
+   ws: vcg_grad_norm_workspace(n) = max(1, ceil(floor(n / 4) / 4096)) * 8 bytes rounded up to a multiple of 16 (host arithmetic,
+   no GPU needed), 16-byte aligned.  csrc/grad_clip.hip. */
+size_t vcg_grad_norm_workspace(size_t n);
+int vcg_grad_norm(const float* g, size_t n, float grad_scale, float max_norm, float* out, void* ws, size_t ws_bytes,
+                  void* stream);
+/* vcg_adam_step with the clip decided on the device: clip = vcg_grad_norm's out.  clip[2] != 0: nothing is written (p, m, v keep
+   their bits).  Otherwise vcg_adam_step with grad_scale replaced by fl32(grad_scale * clip[1]) (one fp32 multiply), the same
+   arithmetic otherwise: for clip[1] == 1.0f vcg_adam_step's result bit for bit. */
+int vcg_adam_step_clipped(float* p, const float* g, float* m, float* v, size_t n,
+                          float step_size, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
+                          float eps, float bc2_sqrt, float grad_scale, const float* clip, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -283,6 +283,27 @@ def _metrics_to_host(named, reducer=None):
     return dict(zip(keys, vec.tolist()))
 
 
+def _max_grad_norm(clip_grad_norm):
+    """configure_optimizers(clip_grad_norm=c) -> FusedAdam's max_grad_norm: 0.0 is off (None: the optimizer allocates and launches
+    nothing new); FusedAdam refuses a negative or non-finite bound."""
+    c = float(clip_grad_norm)
+    return None if c == 0.0 else c
+
+
+def _clip_scalars(**optimizers):
+    """{suffix: optimizer} -> the device scalars a clipping optimizer's last step left in `clip_state`, under the metric names
+    grad_norm<suffix> / grad_skipped<suffix> ("" for the one-optimizer models, "_G" / "_D" otherwise); {} when clipping is off.
+    They join the vector _metrics_to_host copies: still one device->host copy per step.  Under data parallelism every rank holds
+    the same values after the all-reduce, so the rank average returns them unchanged."""
+    out = {}
+    for sfx, opt in optimizers.items():
+        state = getattr(opt, "clip_state", None)
+        if state is not None:
+            out["grad_norm" + sfx] = state[0]
+            out["grad_skipped" + sfx] = state[2]
+    return out
+
+
 def _structural(kwargs):
     """(lambda_ssim, StructuralLoss() or None) of a configure_loss call: with the weight at its default 0 no loss object exists and
     the step computes, launches and reports exactly what it did before the term was added."""
@@ -348,9 +369,9 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
     def forward(self, x):
         return self.decoder(self.encoder(x))
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), decoder_only=False):
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), decoder_only=False, clip_grad_norm=0.0):
         params = self.decoder.parameters() if decoder_only else self.parameters()
-        self.optimizer = FusedAdam(params, lr=lr, betas=betas)
+        self.optimizer = FusedAdam(params, lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
         return self.optimizer
 
     def configure_loss(self, **kwargs):
@@ -382,13 +403,22 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
             m = {"nan_detected": True, "G_loss": float("nan"), "loss_trans": float("nan"), "total_loss": float("nan")}
             if loss_ssim is not None:
                 m["loss_ssim"] = float("nan")
+            if getattr(self.optimizer, "clip_state", None) is not None:      # skipped here, on the host, before any gradient existed
+                m["grad_norm"], m["grad_skipped"] = float("nan"), 1.0
             return m
         _backward_and_step(G_loss, self.optimizer, red)
+        clip = _clip_scalars(**{"": self.optimizer})
         if loss_ssim is not None:
-            m = _metrics_to_host({"G_loss": G_loss, "loss_trans": loss_trans, "loss_ssim": loss_ssim}, red)
-            return {"G_loss": m["G_loss"], "loss_trans": m["loss_trans"], "total_loss": m["G_loss"], "loss_ssim": m["loss_ssim"]}
-        if red is not None:
-            value = _metrics_to_host({"loss_trans": loss_trans}, red)["loss_trans"]      # the global-batch mean, as every other model logs
+            m = _metrics_to_host({"G_loss": G_loss, "loss_trans": loss_trans, "loss_ssim": loss_ssim, **clip}, red)
+            out = {"G_loss": m["G_loss"], "loss_trans": m["loss_trans"], "total_loss": m["G_loss"], "loss_ssim": m["loss_ssim"]}
+            out.update({k: m[k] for k in clip})
+            return out
+        if red is not None or clip:
+            m = _metrics_to_host({"loss_trans": loss_trans, **clip}, red)
+            value = m["loss_trans"]                                               # the global-batch mean, as every other model logs
+            out = {"G_loss": value, "loss_trans": value, "total_loss": value}
+            out.update({k: m[k] for k in clip})
+            return out
         return {"G_loss": value, "loss_trans": value, "total_loss": value}
 
     def validation_step(self, batch):
@@ -434,8 +464,8 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         Gx = self.decoder(self.variational_decoder_block(z))
         return Gx, mu, logvar
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999)):
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas)
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
+        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
         return self.optimizer
 
     def configure_loss(self, **kwargs):
@@ -470,6 +500,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self._check_configured()
         _, named = self._losses(batch)
         _backward_and_step(named["G_loss"], self.optimizer, self.grad_reducer)
+        named.update(_clip_scalars(**{"": self.optimizer}))
         return _metrics_to_host(named, self.grad_reducer)
 
     def validation_step(self, batch):
@@ -579,9 +610,11 @@ class CycleVAEGAN(nn.Module):
         return (Gx, FGx, Fy, GFy, mu_x, logvar_x, mu_FGx, logvar_FGx, mu_y, logvar_y, mu_GFy, logvar_GFy,
                 DYGx, DXFy, DXx, DYy, Gy, Fx)
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999)):
-        self.optimizer_G = FusedAdam(list(self.F.parameters()) + list(self.G.parameters()), lr=lr, betas=betas)
-        self.optimizer_D = FusedAdam(list(self.DX.parameters()) + list(self.DY.parameters()), lr=lr, betas=betas)
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
+        # one bound, two norms: the generators' and the discriminators' gradients are clipped each by their own
+        bound = _max_grad_norm(clip_grad_norm)
+        self.optimizer_G = FusedAdam(list(self.F.parameters()) + list(self.G.parameters()), lr=lr, betas=betas, max_grad_norm=bound)
+        self.optimizer_D = FusedAdam(list(self.DX.parameters()) + list(self.DY.parameters()), lr=lr, betas=betas, max_grad_norm=bound)
         return self.optimizer_G, self.optimizer_D
 
     def save_optimizer_states(self):
@@ -713,6 +746,10 @@ class CycleVAEGAN(nn.Module):
             keys.append("loss_identity")
         if self.loss_ssim is not None:
             keys.append("loss_ssim")
+        if with_means:                                  # the training step: what the two optimizer steps left on the device
+            clip = _clip_scalars(_G=self.optimizer_G, _D=self.optimizer_D)
+            t = dict(t, **clip)
+            keys += list(clip)
         host = _metrics_to_host({k: t[k] for k in keys}, self.grad_reducer if with_means else None)
         out = {"total_loss": host["G_loss"] + host["D_loss"]}
         out.update(host)
@@ -889,8 +926,8 @@ class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
         self.lambda_cycle = 0
         self.lambda_kl = 0
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999)):
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas)
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
+        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
         return self.optimizer
 
     def _check_configured(self, need_opt=True):
@@ -922,10 +959,12 @@ class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
         self._check_configured()
         t, _, _ = self._losses(batch)
         _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
-        host = _metrics_to_host(t, self.grad_reducer)
+        clip = _clip_scalars(**{"": self.optimizer})
+        host = _metrics_to_host(dict(t, **clip), self.grad_reducer)
         m = self._ordered(host)
         if self.paired:
             m["loss_trans"] = host["loss_trans"]
+        m.update({k: host[k] for k in clip})
         return m
 
     def _ordered(self, host):
@@ -1070,8 +1109,8 @@ class DoubleAutoencoder(_OptimizerStatesMixin, nn.Module):
         cycle_ae.F.decoder.load_state_dict(self.decoder_A.state_dict())
         return cycle_ae
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999)):
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas)
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
+        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
         return self.optimizer
 
     def configure_loss(self, **kwargs):
@@ -1091,8 +1130,11 @@ class DoubleAutoencoder(_OptimizerStatesMixin, nn.Module):
             raise ValueError("Optimizer has not been configured yet.")
         t, _, _ = self._losses(batch)
         _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
-        h = _metrics_to_host(t, self.grad_reducer)
-        return {"G_loss": h["G_loss"], "loss_recon_A": h["loss_recon_A"], "loss_recon_B": h["loss_recon_B"], "total_loss": h["G_loss"]}
+        clip = _clip_scalars(**{"": self.optimizer})
+        h = _metrics_to_host(dict(t, **clip), self.grad_reducer)
+        m = {"G_loss": h["G_loss"], "loss_recon_A": h["loss_recon_A"], "loss_recon_B": h["loss_recon_B"], "total_loss": h["G_loss"]}
+        m.update({k: h[k] for k in clip})
+        return m
 
     def validation_step(self, batch):
         if self.loss_fn is None:
@@ -1175,8 +1217,8 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             gen.decoder.load_state_dict(getattr(self, "decoder_" + sfx).state_dict())
         return cycle_vae
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999)):
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas)
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
+        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
         return self.optimizer
 
     def configure_loss(self, **kwargs):
@@ -1200,9 +1242,12 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             raise ValueError("Optimizer has not been configured yet.")
         t, _, _ = self._losses(batch)
         _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
-        h = _metrics_to_host(t, self.grad_reducer)
-        return {"G_loss": h["G_loss"], "loss_recon_A": h["loss_recon_A"], "loss_recon_B": h["loss_recon_B"], "loss_kl": h["loss_kl"],
-                "loss_kl_A": h["loss_kl_A"], "loss_kl_B": h["loss_kl_B"], "total_loss": h["G_loss"]}
+        clip = _clip_scalars(**{"": self.optimizer})
+        h = _metrics_to_host(dict(t, **clip), self.grad_reducer)
+        m = {"G_loss": h["G_loss"], "loss_recon_A": h["loss_recon_A"], "loss_recon_B": h["loss_recon_B"], "loss_kl": h["loss_kl"],
+             "loss_kl_A": h["loss_kl_A"], "loss_kl_B": h["loss_kl_B"], "total_loss": h["G_loss"]}
+        m.update({k: h[k] for k in clip})
+        return m
 
     def validation_step(self, batch):
         if self.loss_trans_fn is None or self.loss_kl_fn is None:
@@ -1222,9 +1267,10 @@ class _SingleGAN(nn.Module):
     (`DGx.detach()`, `retain_graph`, :1277-1287); AEGAN re-runs D on the detached G(x) after the generator update
     (:1105-1108), which reproduces the same outputs because that update does not touch D."""
 
-    def configure_optimizers(self, lr=2e-4, betas=(0.5, 0.999)):
-        self.optimizer_G = FusedAdam(self.G.parameters(), lr=lr, betas=betas)
-        self.optimizer_D = FusedAdam(self.D.parameters(), lr=lr, betas=betas)
+    def configure_optimizers(self, lr=2e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
+        bound = _max_grad_norm(clip_grad_norm)            # one bound, two norms (CycleVAEGAN.configure_optimizers)
+        self.optimizer_G = FusedAdam(self.G.parameters(), lr=lr, betas=betas, max_grad_norm=bound)
+        self.optimizer_D = FusedAdam(self.D.parameters(), lr=lr, betas=betas, max_grad_norm=bound)
         return self.optimizer_G, self.optimizer_D
 
     def save_optimizer_states(self):
@@ -1335,10 +1381,13 @@ class AEGAN(_SingleGAN):
         self._check_configured()
         t, _ = self._losses(batch)
         self._alternating_step(t)
-        h = _metrics_to_host(t, self.grad_reducer)
-        return {"G_loss": h["G_loss"], "D_loss": h["D_loss"], "D_loss_real": h["D_loss_real"], "D_loss_fake": h["D_loss_fake"],
-                "loss_trans": h["loss_trans"], "loss_gan_g": h["gan_g"], "loss_identity": h["loss_identity"],
-                "d_y_mean": h["d_y_mean"], "d_gx_mean": h["d_gx_mean"]}
+        clip = _clip_scalars(_G=self.optimizer_G, _D=self.optimizer_D)
+        h = _metrics_to_host(dict(t, **clip), self.grad_reducer)
+        m = {"G_loss": h["G_loss"], "D_loss": h["D_loss"], "D_loss_real": h["D_loss_real"], "D_loss_fake": h["D_loss_fake"],
+             "loss_trans": h["loss_trans"], "loss_gan_g": h["gan_g"], "loss_identity": h["loss_identity"],
+             "d_y_mean": h["d_y_mean"], "d_gx_mean": h["d_gx_mean"]}
+        m.update({k: h[k] for k in clip})
+        return m
 
     def validation_step(self, batch):
         self._check_configured()            # the reference's AEGAN wants its optimizers even to validate (:1145)
@@ -1405,10 +1454,12 @@ class VAEGAN(_SingleGAN):
             raise ValueError("Optimizers have not been configured yet.")
         t, _ = self._losses(batch)
         self._alternating_step(t)
-        h = _metrics_to_host(t, self.grad_reducer)
+        clip = _clip_scalars(_G=self.optimizer_G, _D=self.optimizer_D)
+        h = _metrics_to_host(dict(t, **clip), self.grad_reducer)
         m = {"G_loss": h["G_loss"], "D_loss": h["D_loss"], "loss_gan_disc_real": h["D_loss_real"],
              "loss_gan_disc_fake": h["D_loss_fake"], "loss_trans": h["loss_trans"], "loss_gan_real": h["gan_g_real"],
              "loss_gan_fake": h["gan_g_fake"], "loss_identity": h["loss_identity"], "loss_kl": h["loss_kl"]}
+        m.update({k: h[k] for k in clip})
         if self.debug_mode:
             m["debug_info"] = self.debug_info
         return m

@@ -745,10 +745,18 @@ __device__ __forceinline__ float adam_v(float v, float g, float gscale, float gg
   }
   return v * b2 + w2 * gg * gg;
 }
+// CLIP (vcg_adam_step_clipped): clip = the four floats vcg_grad_norm left on the device (grad_clip.hip).  clip[2] != 0 (a NaN or
+// Inf in the gradient): the launch writes nothing.  Otherwise gscale becomes fl32(gscale * clip[1]), one fp32 multiply, and the
+// body below is the one vcg_adam_step runs: with clip[1] == 1 the same bits.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g,
                                               float* __restrict__ m, float* __restrict__ v, size_t n,
                                               float step_size, float b2, float w1, float w2, float eps, float bc2_sqrt,
-                                              float gscale) {
+                                              float gscale, const float* __restrict__ clip) {
+  if (CLIP) {
+    if (clip[2] != 0.f) return;
+    gscale = gscale * clip[1];
+  }
   // w1 = 1 - beta1 and w2 = 1 - beta2 arrive rounded from DOUBLE, as torch passes them (lerp_ weight, addcmul_ value):
   // 1.f - 0.999f is 1.3e-5 away from float(1 - 0.999), and that relative error would sit in every exp_avg_sq
   const size_t n4 = n / 4;
@@ -785,9 +793,19 @@ extern "C" int vcg_adam_step(float* p, const float* g, float* m, float* v, size_
                              float one_minus_beta1, float one_minus_beta2, float eps, float bc2_sqrt, float grad_scale, void* stream) {
   VCG_CHECK_ARG(p && g && m && v, "vcg_adam_step: null pointer");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(k_adam, dim3(ew_blocks(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, step_size,
-                     beta2, one_minus_beta1, one_minus_beta2, eps, bc2_sqrt, grad_scale);
+  hipLaunchKernelGGL(k_adam<false>, dim3(ew_blocks(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, step_size,
+                     beta2, one_minus_beta1, one_minus_beta2, eps, bc2_sqrt, grad_scale, (const float*)nullptr);
   VCG_LAUNCH_CHECK("vcg_adam_step");
+  return 0;
+}
+extern "C" int vcg_adam_step_clipped(float* p, const float* g, float* m, float* v, size_t n, float step_size, float beta1, float beta2,
+                                     float one_minus_beta1, float one_minus_beta2, float eps, float bc2_sqrt, float grad_scale,
+                                     const float* clip, void* stream) {
+  VCG_CHECK_ARG(p && g && m && v && clip, "vcg_adam_step_clipped: null pointer");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_adam<true>, dim3(ew_blocks(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, step_size,
+                     beta2, one_minus_beta1, one_minus_beta2, eps, bc2_sqrt, grad_scale, clip);
+  VCG_LAUNCH_CHECK("vcg_adam_step_clipped");
   return 0;
 }
 

@@ -1302,6 +1302,36 @@ def adam_step_flat(p, g, m, v, step, lr, beta1, beta2, eps, grad_scale=1.0):
     PARAM_EPOCH[0] += 1
 
 
+def grad_norm_workspace(n, device):
+    """The slot buffer vcg_grad_norm needs for n gradients (its own allocation: it lives as long as the optimizer)."""
+    return torch.empty(_native.lib().vcg_grad_norm_workspace(int(n)) // 4, dtype=torch.float32, device=device)
+
+
+def grad_norm(flat_grad, grad_scale, max_norm, out, ws):
+    """out[0:4] = [grad_scale * ||flat_grad||_2, min(1, max_norm / (norm + 1e-6)), 1.0 if a gradient is NaN / Inf else 0.0, 0]
+    on the device: one deterministic reduction in double (csrc/grad_clip.hip), nothing comes back to the host."""
+    _require_gpu(flat_grad, "grad_norm")
+    _require_gpu(out, "grad_norm")
+    if not flat_grad.is_contiguous() or out.numel() < 4:
+        raise RuntimeError("grad_norm: flat_grad must be contiguous and out hold four floats")
+    _native.check(_native.lib().vcg_grad_norm(_ptr(flat_grad), flat_grad.numel(), float(grad_scale), float(max_norm), _ptr(out),
+                                              _ptr(ws), ws.numel() * 4, _stream()), "vcg_grad_norm")
+    return out
+
+
+def adam_step_flat_clipped(p, g, m, v, step, lr, beta1, beta2, eps, grad_scale, clip):
+    """adam_step_flat with the gradient scaled by clip[1] on the device, or no update at all where clip[2] != 0
+    (`clip`: what grad_norm wrote)."""
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    step_size = lr / bc1
+    bc2_sqrt = math.sqrt(bc2)
+    _native.check(_native.lib().vcg_adam_step_clipped(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), step_size, beta1, beta2,
+                                                      1.0 - beta1, 1.0 - beta2, eps, bc2_sqrt, grad_scale, _ptr(clip), _stream()),
+                  "vcg_adam_step_clipped")
+    PARAM_EPOCH[0] += 1
+
+
 # ------------------------------------------------------------------ evaluation (test.py)
 def _images_phys(t, what):
     """A logical (N, 3, S, S) image batch -> its (N, S, S, 4) physical buffer (alias or converted copy)."""

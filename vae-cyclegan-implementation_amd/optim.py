@@ -7,10 +7,16 @@ view of a second buffer that the conv backward kernels accumulate into directly.
 optimizer step is therefore ONE kernel launch reading/writing 28 B per parameter, and a
 data-parallel gradient exchange is an all-reduce over contiguous slices of `flat_grad`.
 
+`max_grad_norm` clips the gradient by its global 2-norm, torch.nn.utils.clip_grad_norm_'s definition, without leaving the
+device: one reduction over `flat_grad` (ops.grad_norm) leaves the coefficient in `clip_state`, and the Adam launch reads it
+there.
+
 `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format (per-parameter
 `step`, `exp_avg`, `exp_avg_sq`, one param group) so optimizer states move between the
 reference and this implementation.
 """
+import math
+
 import torch
 
 from . import ops
@@ -19,7 +25,21 @@ _ALIGN = 4  # elements; keeps every view 16-byte aligned for float4 access
 
 
 class FusedAdam:
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    """`max_grad_norm=None`: plain Adam, the launches it always made.  A positive finite float: every step() first measures
+    `grad_scale * ||flat_grad||_2` (the gradient Adam sees: the global-batch gradient under data parallelism; the alignment
+    padding of the buffer is zero and stays zero) and the Adam launches scale the gradient by min(1, max_grad_norm / (norm + 1e-6)).
+    `clip_state` (device, four floats) holds [norm, coefficient, 1.0 if the gradient held a NaN / Inf, 0] of the last step.  A
+    step whose gradient holds a NaN or an Inf writes nothing: parameters and moments keep their bits.  The host does not learn of
+    it without a synchronisation, so the step counters advance as usual: the price of a skipped step is one step of bias
+    correction.  `max_grad_norm` is an attribute of the object only: it is neither in `param_groups` nor in `state_dict()`,
+    whose layout is torch.optim.Adam's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
+                raise ValueError(f"max_grad_norm must be a positive finite number or None, got {max_grad_norm!r}")
+        self.max_grad_norm = max_grad_norm
         plist = []
         seen = set()
         for p in params:
@@ -63,6 +83,11 @@ class FusedAdam:
                              foreach=None, capturable=False, differentiable=False, fused=None,
                              decoupled_weight_decay=False)
         self.param_groups = [dict(self.defaults, params=plist)]
+        self.clip_state = None
+        if max_grad_norm is not None:
+            self.clip_state = torch.empty(4, dtype=torch.float32, device=dev)
+            ops.fill_(self.clip_state, 0.0)
+            self._clip_ws = ops.grad_norm_workspace(off, dev)
         ops.PARAM_EPOCH[0] += 1
 
     # -- torch.optim.Optimizer surface -------------------------------------------------
@@ -85,6 +110,8 @@ class FusedAdam:
         scale = self.grad_scale if grad_scale is None else grad_scale
         self.steps = [t + 1 for t in self.steps]
         self.step_count = max(self.steps)
+        if self.clip_state is not None:
+            ops.grad_norm(self.flat_grad, scale, self.max_grad_norm, self.clip_state, self._clip_ws)
         # one launch per run of consecutive parameters that share a step counter: ONE launch unless a loaded state
         # carried different counters (a reference run that re-created its optimizer for part of the model)
         i = 0
@@ -94,8 +121,12 @@ class FusedAdam:
                 j += 1
             lo = self.offsets[i]
             hi = self.offsets[j + 1] if j + 1 < len(self.params) else self.total
-            ops.adam_step_flat(self.flat_param[lo:hi], self.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
-                               self.steps[i], g["lr"], g["betas"][0], g["betas"][1], g["eps"], scale)
+            if self.clip_state is not None:
+                ops.adam_step_flat_clipped(self.flat_param[lo:hi], self.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                                           self.steps[i], g["lr"], g["betas"][0], g["betas"][1], g["eps"], scale, self.clip_state)
+            else:
+                ops.adam_step_flat(self.flat_param[lo:hi], self.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                                   self.steps[i], g["lr"], g["betas"][0], g["betas"][1], g["eps"], scale)
             i = j + 1
         self._epoch[0] += 1
         if repack:

@@ -16,6 +16,7 @@ Out of scope, as in SURVEY.md §2: TensorBoard and the reference's PIL / torchvi
 import argparse
 import gc
 import json
+import math
 import os
 import sys
 import time
@@ -183,6 +184,17 @@ def validate(model, dataloader, device, args):
     return avg_loss, avg, last_Gx, last_Fy, last_x, last_y
 
 
+def clip_bound(text):
+    """argparse type of --clip_grad_norm: a finite bound >= 0 (0: off)."""
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not math.isfinite(value) or value < 0.0:
+        raise argparse.ArgumentTypeError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {text}")
+    return value
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="Train VAE-CycleGAN models (MI355X-native path)")
     p.add_argument("--architecture", type=str, default="autoencoder", choices=REFERENCE_ARCHS + list(ALIASES))
@@ -206,6 +218,9 @@ def build_parser():
     p.add_argument("--lambda_recon", type=float, default=1.0)
     p.add_argument("--lambda_ssim", type=float, default=0.0,
                    help="weight of the structural term 1 - SSIM beside the L1 (" + ", ".join(SSIM_ARCHS) + "); 0: not computed")
+    p.add_argument("--clip_grad_norm", type=clip_bound, default=0.0,
+                   help="clip each optimizer's gradient to this global 2-norm inside the fused Adam step (every architecture); "
+                        "a step whose gradient holds a NaN / Inf is skipped; 0: off")
     p.add_argument("--output_dir", type=str, default="runs")
     p.add_argument("--save_freq", type=int, default=10)
     p.add_argument("--log_image_freq", type=int, default=5)
@@ -280,6 +295,9 @@ def main(args):
     if getattr(args, "lambda_ssim", 0.0) != 0.0 and args.architecture not in SSIM_ARCHS:
         raise ValueError(f"--lambda_ssim is supported by {', '.join(SSIM_ARCHS)} only, not by {args.architecture}: "
                          "the flag would be ignored")
+    clip = getattr(args, "clip_grad_norm", 0.0)           # (an args object built without the parser)
+    if not math.isfinite(clip) or clip < 0.0:
+        raise ValueError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {clip}")
     # reference train.py:362-377, in its order: the autoencoder / VAE check sees the modalities as given, THEN the
     # per-dataset defaults fill in what was not given (they name the run directory and select hypersim's frames)
     if args.architecture in ("autoencoder", "vae"):
@@ -325,7 +343,7 @@ def main(args):
     torch.manual_seed(args.seed)                     # identical replicas
     ops.manual_seed(ops.rank_seed(args.seed, rank))  # per-rank eps stream
     model = create_model(args.architecture, paired=args.paired, latent_dim=args.latent_dim).to(device)
-    model.configure_optimizers(lr=args.lr)
+    model.configure_optimizers(lr=args.lr, clip_grad_norm=clip)
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
                          lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
                          lambda_ssim=getattr(args, "lambda_ssim", 0.0))
@@ -369,6 +387,9 @@ def main(args):
             print(f"\nEpoch {epoch + 1}/{args.epochs}\nTrain Loss: {train_loss:.4f}   ({ips:.1f} images/s)")
             for k, v in comps.items():
                 print(f"  {k}: {v:.6f}")
+            for k, v in comps.items():               # what the reference's unused `nan_count` was for (train.py:90)
+                if k.startswith("grad_skipped"):
+                    print(f"  steps skipped for a NaN / Inf gradient ({k}): {round(v * len(loader))} of {len(loader)}")
         # on the test set (reference train.py:533-537: every log_image_freq epochs); here a held-out synthetic stream.
         # validation_step has no exchange in it: every rank validates its shard of the test set and `validate` averages
         # the metrics over ranks
