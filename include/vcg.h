@@ -369,6 +369,23 @@ int vcg_adam_step_clipped(float* p, const float* g, float* m, float* v, size_t n
                           float step_size, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2,
                           float eps, float bc2_sqrt, float grad_scale, const float* clip, void* stream);
 
+/* Averaged weights (new: the reference has none) — csrc/ema.hip -------------------------------------------------------------- */
+/* One step of an exponential moving average e of the n parameters p, in place on e:
+     e[i] = fmaf(w, p[i] - e[i], e[i]),   w = (float)(1 - decay), computed in double by the caller and rounded once.
+   p is read only.  w == 1.0f copies (e[i] = p[i] exactly: the rounded p - e would not give p back); w == 0 launches nothing and
+   leaves e bit for bit.  An element with e[i] == p[i] keeps its value for every w.
+   skip: null, or the four floats vcg_grad_norm left on the device: where skip[2] != 0 (the gradient held a NaN / Inf, so
+   vcg_adam_step_clipped wrote nothing) this call writes nothing either.
+   One float4 per lane over grids of at most 2048 x 256 lanes, the n % 4 last elements one by one; vector loads and stores only,
+   no atomics, no workspace: the same input gives the same bits on every call.
+   Refused (non-zero, vcg_last_error, nothing launched): e or p null; e or p not 16-byte aligned; w NaN, infinite or outside
+   [0, 1].  e and p must not overlap.  n == 0 is a no-op. */
+int vcg_ema_update(float* e, const float* p, size_t n, float w, const float* skip, void* stream);
+/* a[i] <-> b[i] for n 4-byte words in one pass (bit patterns move as they are: a NaN keeps its payload); twice is the identity.
+   The launch shape of vcg_ema_update; 16 B of traffic per element.  Refused: a or b null, a or b not 16-byte aligned, ranges
+   [a, a + n) and [b, b + n) that overlap.  n == 0 is a no-op. */
+int vcg_swap(float* a, float* b, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

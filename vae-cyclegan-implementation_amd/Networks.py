@@ -11,6 +11,7 @@ two-stage InstanceNorm statistics, and a normalise(+activation)(+residual)(+Pixe
 Tensors crossing module boundaries keep the logical (N, C, H, W) shape and are stored
 NHWC (pitch 4 for 3-channel images); NCHW-contiguous inputs are converted on entry.
 """
+import contextlib
 import math
 
 import torch
@@ -290,6 +291,15 @@ def _max_grad_norm(clip_grad_norm):
     return None if c == 0.0 else c
 
 
+def _ema_decay(ema_decay):
+    """configure_optimizers(ema_decay=d) -> FusedAdam's ema_decay: 0.0 is off (None: the optimizer allocates and launches nothing
+    new); anything else must be finite and lie in [0, 1)."""
+    d = float(ema_decay)
+    if not math.isfinite(d) or not 0.0 <= d < 1.0:
+        raise ValueError(f"ema_decay must be finite and lie in [0, 1) (0 switches the averaged weights off), got {ema_decay!r}")
+    return None if d == 0.0 else d
+
+
 def _clip_scalars(**optimizers):
     """{suffix: optimizer} -> the device scalars a clipping optimizer's last step left in `clip_state`, under the metric names
     grad_norm<suffix> / grad_skipped<suffix> ("" for the one-optimizer models, "_G" / "_D" otherwise); {} when clipping is off.
@@ -325,7 +335,79 @@ def _backward_and_step(loss, optimizer, reducer):
     optimizer.step()
 
 
-class _OptimizerStatesMixin:
+def _refuse_training_in_ema_scope(model):
+    """First line of every training_step (a caller's stand-in for `self` need not know the attribute)."""
+    if getattr(model, "_ema_in_scope", False):
+        raise RuntimeError("training_step inside ema_scope(): the parameters hold the averaged weights; leave the scope first")
+
+
+class _EmaMixin:
+    """Averaged generator weights of a model whose configure_optimizers was given ema_decay > 0.  The average follows the
+    optimizer that trains generators — `optimizer_G` of the GAN models, `optimizer` of the others — and lives in that optimizer
+    (FusedAdam.flat_ema); the discriminators are not averaged.  Parameters are all there is to average: the generators hold no
+    buffers (InstanceNorm keeps no running statistics here); the only buffers of any model are the discriminators'
+    spectral-norm `weight_u` / `weight_v`."""
+    _ema_in_scope = False
+
+    def _ema_optimizer(self):
+        opt = getattr(self, "optimizer_G", None)
+        if opt is None:
+            opt = getattr(self, "optimizer", None)
+        return opt if opt is not None and getattr(opt, "ema_decay", None) is not None else None
+
+    @property
+    def ema_enabled(self):
+        return self._ema_optimizer() is not None
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """The averaged weights in the parameters' place for the duration of the block (evaluation), the raw ones back afterwards,
+        also when the block raises.  Does nothing when the model keeps no average.  Not re-entrant."""
+        if self._ema_in_scope:
+            raise RuntimeError("ema_scope() is already active on this model: it does not nest")
+        opt = self._ema_optimizer()
+        if opt is None:
+            yield self
+            return
+        opt.swap_ema()
+        self._ema_in_scope = True
+        try:
+            yield self
+        finally:
+            self._ema_in_scope = False
+            opt.swap_ema()
+
+    def _ema_names(self, opt):
+        names = {id(p): name for name, p in self.named_parameters()}
+        return [names[id(p)] for p in opt.params]
+
+    def ema_state_dict(self):
+        """{state_dict key: averaged tensor} of the tracked parameters: state_dict()'s names and OIHW shapes."""
+        opt = self._ema_optimizer()
+        if opt is None:
+            raise RuntimeError("ema_state_dict(): this model keeps no averaged weights (configure_optimizers(ema_decay=...))")
+        return dict(zip(self._ema_names(opt), opt.ema_state()["tensors"]))
+
+    def save_ema_state(self):
+        """{"decay", "updates", "state_dict": ema_state_dict()} — what a checkpoint stores under `vcg_ema`."""
+        sd = self.ema_state_dict()
+        opt = self._ema_optimizer()
+        return {"decay": opt.ema_decay, "updates": opt.ema_updates, "state_dict": sd}
+
+    def load_ema_state(self, state):
+        opt = self._ema_optimizer()
+        if opt is None:
+            raise RuntimeError("load_ema_state(): this model keeps no averaged weights (configure_optimizers(ema_decay=...))")
+        names, sd = self._ema_names(opt), state["state_dict"]
+        missing = [n for n in names if n not in sd]
+        if missing or len(sd) != len(names):
+            extra = sorted(set(sd) - set(names))
+            raise KeyError(f"averaged weights do not match the tracked parameters: missing {missing[:3]}, unexpected {extra[:3]} "
+                           f"({len(sd)} saved, {len(names)} tracked)")
+        opt.load_ema_state({"updates": state["updates"], "tensors": [sd[n] for n in names]})
+
+
+class _OptimizerStatesMixin(_EmaMixin):
     _opt_names = ("optimizer",)
 
     def save_optimizer_states(self):
@@ -369,9 +451,10 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
     def forward(self, x):
         return self.decoder(self.encoder(x))
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), decoder_only=False, clip_grad_norm=0.0):
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), decoder_only=False, clip_grad_norm=0.0, ema_decay=0.0):
         params = self.decoder.parameters() if decoder_only else self.parameters()
-        self.optimizer = FusedAdam(params, lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
+        self.optimizer = FusedAdam(params, lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
+                                   ema_decay=_ema_decay(ema_decay))
         return self.optimizer
 
     def configure_loss(self, **kwargs):
@@ -379,6 +462,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
 
     def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
         if self.loss_fn is None:
             raise ValueError("Loss function has not been configured yet.")
         if self.optimizer is None:
@@ -464,8 +548,9 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         Gx = self.decoder(self.variational_decoder_block(z))
         return Gx, mu, logvar
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
+                                   ema_decay=_ema_decay(ema_decay))
         return self.optimizer
 
     def configure_loss(self, **kwargs):
@@ -497,6 +582,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         return output, named
 
     def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
         self._check_configured()
         _, named = self._losses(batch)
         _backward_and_step(named["G_loss"], self.optimizer, self.grad_reducer)
@@ -554,7 +640,7 @@ def _ae_pair(ae_a, a, ae_b, b, fork):
     return ra, rb
 
 
-class CycleVAEGAN(nn.Module):
+class CycleVAEGAN(_EmaMixin, nn.Module):
     """Two VAEs (G: X->Y, F: Y->X) + two discriminators; cycle + LSGAN + KL (+identity if paired);
     alternating G then D update  (reference Networks.py:1872-2150).
 
@@ -610,10 +696,11 @@ class CycleVAEGAN(nn.Module):
         return (Gx, FGx, Fy, GFy, mu_x, logvar_x, mu_FGx, logvar_FGx, mu_y, logvar_y, mu_GFy, logvar_GFy,
                 DYGx, DXFy, DXx, DYy, Gy, Fx)
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
         # one bound, two norms: the generators' and the discriminators' gradients are clipped each by their own
         bound = _max_grad_norm(clip_grad_norm)
-        self.optimizer_G = FusedAdam(list(self.F.parameters()) + list(self.G.parameters()), lr=lr, betas=betas, max_grad_norm=bound)
+        self.optimizer_G = FusedAdam(list(self.F.parameters()) + list(self.G.parameters()), lr=lr, betas=betas, max_grad_norm=bound,
+                                     ema_decay=_ema_decay(ema_decay))            # the generators' average; none for DX, DY
         self.optimizer_D = FusedAdam(list(self.DX.parameters()) + list(self.DY.parameters()), lr=lr, betas=betas, max_grad_norm=bound)
         return self.optimizer_G, self.optimizer_D
 
@@ -756,6 +843,7 @@ class CycleVAEGAN(nn.Module):
         return out
 
     def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
         self._check_configured()
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         g_params = self.optimizer_G.params
@@ -926,8 +1014,9 @@ class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
         self.lambda_cycle = 0
         self.lambda_kl = 0
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
+                                   ema_decay=_ema_decay(ema_decay))
         return self.optimizer
 
     def _check_configured(self, need_opt=True):
@@ -956,6 +1045,7 @@ class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
         return t, Gx, Fy
 
     def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
         self._check_configured()
         t, _, _ = self._losses(batch)
         _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
@@ -1109,8 +1199,9 @@ class DoubleAutoencoder(_OptimizerStatesMixin, nn.Module):
         cycle_ae.F.decoder.load_state_dict(self.decoder_A.state_dict())
         return cycle_ae
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
+                                   ema_decay=_ema_decay(ema_decay))
         return self.optimizer
 
     def configure_loss(self, **kwargs):
@@ -1124,6 +1215,7 @@ class DoubleAutoencoder(_OptimizerStatesMixin, nn.Module):
         return t, x, y
 
     def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
         if self.loss_fn is None:
             raise ValueError("Loss function has not been configured yet.")
         if self.optimizer is None:
@@ -1217,8 +1309,9 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             gen.decoder.load_state_dict(getattr(self, "decoder_" + sfx).state_dict())
         return cycle_vae
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm))
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
+                                   ema_decay=_ema_decay(ema_decay))
         return self.optimizer
 
     def configure_loss(self, **kwargs):
@@ -1236,6 +1329,7 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         return t, x, y
 
     def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
         if self.loss_trans_fn is None or self.loss_kl_fn is None:
             raise ValueError("Loss functions have not been configured yet.")
         if self.optimizer is None:
@@ -1260,16 +1354,16 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
                     "loss_kl_B": h["loss_kl_B"], "Gx": self.translate_A_to_B(x), "Fy": self.translate_B_to_A(y)}
 
 
-class _SingleGAN(nn.Module):
+class _SingleGAN(_EmaMixin, nn.Module):
     """One generator G: X->Y and one discriminator D on Y, alternating G / D updates — the shared step of AEGAN and VAEGAN
     (reference Networks.py:991-1348).  As in CycleVAEGAN the discriminator runs once per step: the G phase takes its data
     gradient, the D phase its weight gradients from the same activations.  VAEGAN is written that way in the reference
     (`DGx.detach()`, `retain_graph`, :1277-1287); AEGAN re-runs D on the detached G(x) after the generator update
     (:1105-1108), which reproduces the same outputs because that update does not touch D."""
 
-    def configure_optimizers(self, lr=2e-4, betas=(0.5, 0.999), clip_grad_norm=0.0):
+    def configure_optimizers(self, lr=2e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
         bound = _max_grad_norm(clip_grad_norm)            # one bound, two norms (CycleVAEGAN.configure_optimizers)
-        self.optimizer_G = FusedAdam(self.G.parameters(), lr=lr, betas=betas, max_grad_norm=bound)
+        self.optimizer_G = FusedAdam(self.G.parameters(), lr=lr, betas=betas, max_grad_norm=bound, ema_decay=_ema_decay(ema_decay))
         self.optimizer_D = FusedAdam(self.D.parameters(), lr=lr, betas=betas, max_grad_norm=bound)
         return self.optimizer_G, self.optimizer_D
 
@@ -1378,6 +1472,7 @@ class AEGAN(_SingleGAN):
         return t, Gx
 
     def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
         self._check_configured()
         t, _ = self._losses(batch)
         self._alternating_step(t)
@@ -1450,6 +1545,7 @@ class VAEGAN(_SingleGAN):
         return t, Gx
 
     def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
         if self.optimizer_G is None or self.optimizer_D is None:
             raise ValueError("Optimizers have not been configured yet.")
         t, _ = self._losses(batch)

@@ -1332,6 +1332,33 @@ def adam_step_flat_clipped(p, g, m, v, step, lr, beta1, beta2, eps, grad_scale, 
     PARAM_EPOCH[0] += 1
 
 
+def ema_update(ema, param, weight, skip=None):
+    """ema += weight * (param - ema) in place, one launch (csrc/ema.hip); `weight` = 1 - decay as a Python float (double), rounded
+    to fp32 once on the way in.  weight 1 copies, weight 0 launches nothing.  `skip`: FusedAdam.clip_state or None: a step Adam
+    skipped for a NaN / Inf gradient leaves the average alone too."""
+    _require_gpu(ema, "ema_update")
+    _require_gpu(param, "ema_update")
+    if not ema.is_contiguous() or not param.is_contiguous() or ema.numel() != param.numel():
+        raise RuntimeError("ema_update: ema and param must be contiguous and of one size")
+    if skip is not None:
+        _require_gpu(skip, "ema_update")
+        if not skip.is_contiguous() or skip.numel() < 4:
+            raise RuntimeError("ema_update: skip must hold the four floats grad_norm wrote")
+    _native.check(_native.lib().vcg_ema_update(_ptr(ema), _ptr(param), ema.numel(), float(weight), _ptr(skip), _stream()),
+                  "vcg_ema_update")
+    return ema
+
+
+def swap_(a, b):
+    """Exchange the contents of two flat buffers in place, one launch (csrc/ema.hip).  The caller orders it against other
+    streams and bumps the parameter epochs if one of the two holds parameters (FusedAdam.swap_ema)."""
+    _require_gpu(a, "swap_")
+    _require_gpu(b, "swap_")
+    if not a.is_contiguous() or not b.is_contiguous() or a.numel() != b.numel():
+        raise RuntimeError("swap_: the two tensors must be contiguous and of one size")
+    _native.check(_native.lib().vcg_swap(_ptr(a), _ptr(b), a.numel(), _stream()), "vcg_swap")
+
+
 # ------------------------------------------------------------------ evaluation (test.py)
 def _images_phys(t, what):
     """A logical (N, 3, S, S) image batch -> its (N, S, S, 4) physical buffer (alias or converted copy)."""

@@ -11,6 +11,9 @@ data-parallel gradient exchange is an all-reduce over contiguous slices of `flat
 device: one reduction over `flat_grad` (ops.grad_norm) leaves the coefficient in `clip_state`, and the Adam launch reads it
 there.
 
+`ema_decay` keeps an exponential moving average of the parameters in a buffer of its own (`flat_ema`), updated by one extra launch
+per step (csrc/ema.hip): the Adam kernel is not involved.  `swap_ema()` exchanges the average with the parameters for an evaluation.
+
 `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format (per-parameter
 `step`, `exp_avg`, `exp_avg_sq`, one param group) so optimizer states move between the
 reference and this implementation.
@@ -24,6 +27,16 @@ from . import ops
 _ALIGN = 4  # elements; keeps every view 16-byte aligned for float4 access
 
 
+def ema_decay_at(ema_decay, updates):
+    """The decay of the update that follows `updates` completed ones: 0 for the first (it copies the parameters: whatever was
+    loaded or broadcast after the optimizer was built is what the average starts from), then the usual warm-up
+    min(ema_decay, (1 + k) / (10 + k)), which climbs from 2/11 to `ema_decay` and stays there."""
+    k = int(updates)
+    if k <= 0:
+        return 0.0
+    return min(float(ema_decay), (1.0 + k) / (10.0 + k))
+
+
 class FusedAdam:
     """`max_grad_norm=None`: plain Adam, the launches it always made.  A positive finite float: every step() first measures
     `grad_scale * ||flat_grad||_2` (the gradient Adam sees: the global-batch gradient under data parallelism; the alignment
@@ -32,9 +45,21 @@ class FusedAdam:
     step whose gradient holds a NaN or an Inf writes nothing: parameters and moments keep their bits.  The host does not learn of
     it without a synchronisation, so the step counters advance as usual: the price of a skipped step is one step of bias
     correction.  `max_grad_norm` is an attribute of the object only: it is neither in `param_groups` nor in `state_dict()`,
-    whose layout is torch.optim.Adam's."""
+    whose layout is torch.optim.Adam's.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None):
+    `ema_decay=None`: no average: no buffer, no launch.  A float in (0, 1): `flat_ema` (the size of `flat_param`, its alignment
+    padding zero like the parameters') follows the parameters: after the Adam launches of every step(), ONE launch over the whole
+    buffer on the same stream does ema += (1 - d) (param - ema) with d = ema_decay_at(ema_decay, ema_updates).  With clipping
+    configured the launch reads `clip_state` too and writes nothing where Adam wrote nothing.  The host cannot see such a skipped
+    step, so `ema_updates` advances regardless, as the step counters do: the price is one step of the warm-up schedule.
+    The average is not part of `state_dict()` or `param_groups`; `ema_state()` / `load_ema_state()` carry it."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, ema_decay=None):
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not (math.isfinite(ema_decay) and 0.0 < ema_decay < 1.0):
+                raise ValueError(f"ema_decay must lie in (0, 1) or be None, got {ema_decay!r}")
+        self.ema_decay = ema_decay
         if max_grad_norm is not None:
             max_grad_norm = float(max_grad_norm)
             if not (math.isfinite(max_grad_norm) and max_grad_norm > 0.0):
@@ -88,6 +113,12 @@ class FusedAdam:
             self.clip_state = torch.empty(4, dtype=torch.float32, device=dev)
             ops.fill_(self.clip_state, 0.0)
             self._clip_ws = ops.grad_norm_workspace(off, dev)
+        self.flat_ema = None
+        if ema_decay is not None:
+            self.flat_ema = torch.empty(off, dtype=torch.float32, device=dev)
+            ops.fill_(self.flat_ema, 0.0)
+            self.ema_updates = 0
+            self.ema_swapped = False              # True while flat_param holds the average (swap_ema)
         ops.PARAM_EPOCH[0] += 1
 
     # -- torch.optim.Optimizer surface -------------------------------------------------
@@ -106,6 +137,8 @@ class FusedAdam:
         """`grad_scale` multiplies the gradient inside the fused launch (1/world after a summing
         all-reduce; parallel.GradReducer sets `self.grad_scale`).  `repack=False` leaves the side-stream repack of
         the conv weights to the caller (ops.repack_async), e.g. until no collective is in flight any more."""
+        if self.flat_ema is not None and self.ema_swapped:
+            raise RuntimeError("step() while the averaged weights are swapped in (swap_ema / ema_scope): swap them out first")
         g = self.param_groups[0]
         scale = self.grad_scale if grad_scale is None else grad_scale
         self.steps = [t + 1 for t in self.steps]
@@ -128,9 +161,66 @@ class FusedAdam:
                 ops.adam_step_flat(self.flat_param[lo:hi], self.flat_grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
                                    self.steps[i], g["lr"], g["betas"][0], g["betas"][1], g["eps"], scale)
             i = j + 1
+        if self.flat_ema is not None:
+            ops.ema_update(self.flat_ema, self.flat_param, 1.0 - ema_decay_at(self.ema_decay, self.ema_updates), self.clip_state)
+            self.ema_updates += 1
         self._epoch[0] += 1
         if repack:
             ops.repack_async(self.params)
+
+    # -- averaged weights ---------------------------------------------------------------
+    def _require_ema(self, what, swapped=False):
+        if self.flat_ema is None:
+            raise RuntimeError(f"{what}: this optimizer keeps no average (ema_decay=None)")
+        if self.ema_swapped and not swapped:
+            raise RuntimeError(f"{what} while the averaged weights are swapped in: swap them out first")
+
+    def _seed_ema(self):
+        """An average that no update has reached yet IS the parameters (the first update would copy them anyway)."""
+        if self.ema_updates == 0:
+            ops.ema_update(self.flat_ema, self.flat_param, 1.0)
+
+    def ema_state(self):
+        """{"decay", "updates", "tensors": one clone per parameter, shaped like it}."""
+        self._require_ema("ema_state()")
+        self._seed_ema()
+        return {"decay": self.ema_decay, "updates": self.ema_updates,
+                "tensors": [self.flat_ema[o:o + p.numel()].view(p.shape).clone() for p, o in zip(self.params, self.offsets)]}
+
+    def load_ema_state(self, state):
+        """What ema_state() returned (tensors on any device).  The decay stays the configured one."""
+        self._require_ema("load_ema_state()")
+        tensors = list(state["tensors"])
+        if len(tensors) != len(self.params):
+            raise ValueError(f"averaged weights for {len(tensors)} parameter(s), this optimizer holds {len(self.params)}: "
+                             "they were saved for another parameter list")
+        for i, (t, p) in enumerate(zip(tensors, self.params)):
+            if tuple(t.shape) != tuple(p.shape):
+                raise ValueError(f"averaged weight {i} has shape {tuple(t.shape)}, expected {tuple(p.shape)}")
+        updates = int(state["updates"])
+        if updates < 0:
+            raise ValueError(f"averaged weights with a negative update count {updates}")
+        with torch.no_grad():
+            for t, p, o in zip(tensors, self.params, self.offsets):
+                self.flat_ema[o:o + p.numel()].view(p.shape).copy_(t)
+        self.ema_updates = updates
+
+    def swap_ema(self):
+        """Exchange parameters and average in place (one launch); every weight pack is rebuilt at its next use.  Twice is the
+        identity, bit for bit."""
+        self._require_ema("swap_ema()", swapped=True)
+        if not self.ema_swapped:
+            self._seed_ema()
+        # What orders the swap: the packs of the last step are written on the weight-gradient side stream (ops.repack_async)
+        # and, in a two-direction forward, on the second direction's stream; both READ the parameters.  join_side_streams
+        # makes the current stream wait for everything issued on either, so the exchange starts after their last read.  Readers
+        # that come later are ordered the usual way: a pack is keyed on the epochs bumped below, is rebuilt on the stream
+        # that first needs it, and a forked stream waits for the current one when it forks (ops.DirectionFork).
+        ops.join_side_streams()
+        ops.swap_(self.flat_param, self.flat_ema)
+        self.ema_swapped = not self.ema_swapped
+        self._epoch[0] += 1
+        ops.PARAM_EPOCH[0] += 1
 
     def state_dict(self):
         state = {}

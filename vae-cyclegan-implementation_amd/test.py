@@ -58,6 +58,9 @@ def build_parser():
     p.add_argument("--batch_size", type=int, default=1)
     p.add_argument("--seed", type=int, default=1234, help="summer2winter y draws and the VAE eps stream")
     p.add_argument("--save_images", action="store_true", help="write every G(x) as a PNG")
+    p.add_argument("--ema", action="store_true",
+                   help="evaluate the averaged generator weights of runs trained with --ema_decay (a run without them is reported "
+                        "and skipped)")
     p.add_argument("--reference_split", action="store_true",
                    help="hypersim: evaluate on the reference test.py's random_split(seed 42) subset instead of the run's own")
     return p
@@ -123,11 +126,12 @@ def translate(model, architecture, x):
     raise ValueError(f"Unknown architecture: {architecture}")
 
 
-def load_model(run, device):
-    """test.py:110-143: the model of `run` built from its args.json, with its checkpoint's parameters, in eval mode."""
+def load_model(run, device, ema=False):
+    """test.py:110-143: the model of `run` built from its args.json, with its checkpoint's parameters (`ema`: its averaged
+    generator weights, utils.load_model_weights), in eval mode."""
     a = run["args"]
     model = train.create_model(run["architecture"], paired=a.get("paired", True), latent_dim=a.get("latent_dim", 64)).to(device)
-    ck = utils.load_model_weights(model, run["best_model_path"])
+    ck = utils.load_model_weights(model, run["best_model_path"], ema=ema)
     model.eval()
     loss = ck.get("loss")
     print(f"  Loaded {run['architecture']} from epoch {ck.get('epoch', 'unknown')}"
@@ -302,7 +306,7 @@ def evaluate_model_group(runs, device, output_dir, args, unpaired=False):
         done = []
         for run in group:
             try:
-                model = load_model(run, device)
+                model = load_model(run, device, ema=getattr(args, "ema", False))
             except Exception as e:                       # as the reference: a run that does not load is reported and skipped
                 print(f"Error loading {run['run_name']}: {e}")
                 continue

@@ -195,6 +195,17 @@ def clip_bound(text):
     return value
 
 
+def ema_decay_value(text):
+    """argparse type of --ema_decay: a finite decay in [0, 1) (0: off)."""
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not math.isfinite(value) or not 0.0 <= value < 1.0:
+        raise argparse.ArgumentTypeError(f"--ema_decay must be finite and lie in [0, 1) (0 switches the averaged weights off), got {text}")
+    return value
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="Train VAE-CycleGAN models (MI355X-native path)")
     p.add_argument("--architecture", type=str, default="autoencoder", choices=REFERENCE_ARCHS + list(ALIASES))
@@ -221,6 +232,10 @@ def build_parser():
     p.add_argument("--clip_grad_norm", type=clip_bound, default=0.0,
                    help="clip each optimizer's gradient to this global 2-norm inside the fused Adam step (every architecture); "
                         "a step whose gradient holds a NaN / Inf is skipped; 0: off")
+    p.add_argument("--ema_decay", type=ema_decay_value, default=0.0,
+                   help="keep an exponential moving average of the generator weights with this decay (e.g. 0.999, warmed up from "
+                        "the first step); the test loss that selects best_model.pth is then the averaged weights', and test.py / "
+                        "translate.py --ema load them; 0: off")
     p.add_argument("--output_dir", type=str, default="runs")
     p.add_argument("--save_freq", type=int, default=10)
     p.add_argument("--log_image_freq", type=int, default=5)
@@ -298,6 +313,9 @@ def main(args):
     clip = getattr(args, "clip_grad_norm", 0.0)           # (an args object built without the parser)
     if not math.isfinite(clip) or clip < 0.0:
         raise ValueError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {clip}")
+    ema_decay = getattr(args, "ema_decay", 0.0)
+    if not math.isfinite(ema_decay) or not 0.0 <= ema_decay < 1.0:
+        raise ValueError(f"--ema_decay must be finite and lie in [0, 1) (0 switches the averaged weights off), got {ema_decay}")
     # reference train.py:362-377, in its order: the autoencoder / VAE check sees the modalities as given, THEN the
     # per-dataset defaults fill in what was not given (they name the run directory and select hypersim's frames)
     if args.architecture in ("autoencoder", "vae"):
@@ -343,7 +361,9 @@ def main(args):
     torch.manual_seed(args.seed)                     # identical replicas
     ops.manual_seed(ops.rank_seed(args.seed, rank))  # per-rank eps stream
     model = create_model(args.architecture, paired=args.paired, latent_dim=args.latent_dim).to(device)
-    model.configure_optimizers(lr=args.lr, clip_grad_norm=clip)
+    model.configure_optimizers(lr=args.lr, clip_grad_norm=clip, ema_decay=ema_decay)
+    if ema_decay > 0.0 and rank == 0:
+        print(f"Averaged generator weights (decay {ema_decay}): the test loss, and with it best_model.pth, is the averaged weights'")
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
                          lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
                          lambda_ssim=getattr(args, "lambda_ssim", 0.0))
@@ -396,7 +416,8 @@ def main(args):
         if args.log_image_freq > 0 and epoch % args.log_image_freq == 0 and not (image_loaders and image_loaders[1] is None):
             test_loader = image_loaders[1] if image_loaders else SyntheticLoader(
                 args.batch_size, args.image_size, max(1, args.steps_per_epoch // 10), device, args.seed + 1, rank, same_xy, epoch)
-            test_loss, test_comps, *_ = validate(model, test_loader, device, args)
+            with model.ema_scope():                  # the averaged weights, when the run keeps them; the raw ones otherwise
+                test_loss, test_comps, *_ = validate(model, test_loader, device, args)
             if rank == 0:
                 print(f"Test Loss: {test_loss:.4f}")
                 for k, v in test_comps.items():

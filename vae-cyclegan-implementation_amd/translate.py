@@ -40,9 +40,10 @@ VARIATIONAL = ("vae", "vaegan", "cyclevae", "cyclevaegan", "doublevae")
 
 
 # ------------------------------------------------------------------ the model
-def load_generator(checkpoint_or_run_dir, architecture=None, latent_dim=None, paired=None, device="cuda"):
+def load_generator(checkpoint_or_run_dir, architecture=None, latent_dim=None, paired=None, device="cuda", ema=False):
     """(model in eval mode, architecture) from a run directory (its args.json + best_model.pth, as test.load_model) or from a
-    bare .pth plus the arguments args.json would have given.  Parameters only: no optimizer state is loaded."""
+    bare .pth plus the arguments args.json would have given.  Parameters only: no optimizer state is loaded.  `ema`: the
+    checkpoint's averaged generator weights instead of the raw ones (a KeyError if it has none)."""
     path = Path(checkpoint_or_run_dir)
     if path.is_dir():
         with open(path / "args.json") as f:
@@ -56,7 +57,7 @@ def load_generator(checkpoint_or_run_dir, architecture=None, latent_dim=None, pa
     architecture = train.ALIASES.get(architecture, architecture)
     model = train.create_model(architecture, paired=True if paired is None else paired,
                                latent_dim=64 if latent_dim is None else latent_dim).to(device)
-    utils.load_model_weights(model, str(path))
+    utils.load_model_weights(model, str(path), ema=ema)
     model.eval()
     return model, architecture
 
@@ -222,6 +223,7 @@ def build_parser():
                    help="first resize every frame to SIZE x SIZE (the reference's Resize((S, S)); a multiple of 16, at least 32)")
     p.add_argument("--targets", type=str, default=None,
                    help="directory with the expected images under the same file names: writes metrics.json (L1, MSE, PSNR, SSIM)")
+    p.add_argument("--ema", action="store_true", help="use the checkpoint's averaged generator weights (a run trained with --ema_decay)")
     p.add_argument("--suffix", type=str, default="_translated")
     p.add_argument("--num_workers", type=int, default=4, help="host threads that decode and write images")
     return p
@@ -309,7 +311,7 @@ def main(argv=None):
     if args.size is not None and (args.size < ops.MIN_TRANSLATE_SIDE or args.size % 16):
         raise ValueError(f"--size must be a multiple of 16 and at least {ops.MIN_TRANSLATE_SIDE}")
     device = _device()
-    model, architecture = load_generator(args.checkpoint, args.architecture, args.latent_dim, None, device)
+    model, architecture = load_generator(args.checkpoint, args.architecture, args.latent_dim, None, device, ema=args.ema)
     generator_of(model, architecture, args.direction)               # a direction the model does not have: fail before any file
     paths = discover_inputs(args.input)
     if not paths:

@@ -39,7 +39,12 @@ def save_checkpoint(model, epoch, loss, args, filename, best_test_loss=None):
     Under data parallelism one rank writes the file but every rank draws from its OWN eps stream
     (`ops.rank_seed(base, rank)`): what is saved is the BASE seed (the writer's seed with its rank offset taken out) and
     the stream offset, which is the same on all ranks (they run identical steps); `load_checkpoint` re-derives each
-    rank's seed from the base."""
+    rank's seed from the base.
+
+    A model that keeps averaged generator weights (configure_optimizers(ema_decay=...)) adds a third key, `vcg_ema` =
+    {"decay", "updates", "state_dict"}: the average under state_dict()'s names, for the tracked parameters only.  It is absent
+    otherwise, and `model_state_dict` is the raw weights either way: a resumed run continues from what it trained, and the
+    reference's loader reads the file as before."""
     rank = _rank()
     seed = int(ops._RNG["seed"])
     checkpoint = {
@@ -52,6 +57,8 @@ def save_checkpoint(model, epoch, loss, args, filename, best_test_loss=None):
     }
     if best_test_loss is not None:
         checkpoint["vcg_best_test_loss"] = float(best_test_loss)
+    if getattr(model, "ema_enabled", False):
+        checkpoint["vcg_ema"] = _to_cpu(model.save_ema_state())
     torch.save(checkpoint, filename)
     print(f"Checkpoint saved to {filename}")
 
@@ -81,20 +88,36 @@ def load_checkpoint(model, filename, device):
         ops._RNG["offset"] = int(rng["offset"])
     if "vcg_best_test_loss" in checkpoint:
         LAST_EXTRAS["best_test_loss"] = float(checkpoint["vcg_best_test_loss"])
+    if getattr(model, "ema_enabled", False):             # (a `vcg_ema` key in the file of a run without averaging is ignored)
+        if "vcg_ema" in checkpoint:
+            model.load_ema_state(checkpoint["vcg_ema"])
+        else:
+            print(f"{filename} holds no averaged weights: the average starts from the loaded weights")
     ops.PARAM_EPOCH[0] += 1                              # load_state_dict wrote through .data: drop every weight pack
     epoch, loss = checkpoint["epoch"], checkpoint["loss"]
     print(f"Loaded checkpoint from {filename} (epoch {epoch}, loss {loss:.4f})")
     return epoch, loss
 
 
-def load_model_weights(model, filename):
+def load_model_weights(model, filename, ema=False):
     """test.py:110-143: the parameters of a checkpoint and nothing else, for inference.  Unlike `load_checkpoint` this configures
     no optimizer, loads no Adam state (which would double the memory of every loaded model) and leaves the eps stream alone (the
-    evaluator seeds it itself).  Returns the checkpoint's other entries (epoch, loss, args)."""
+    evaluator seeds it itself).  `ema=True`: the averaged generator weights of the checkpoint (`vcg_ema`) in place of the raw ones,
+    for the parameters that were averaged; everything else (discriminators) as trained.  Returns the checkpoint's other entries
+    (epoch, loss, args)."""
     if not os.path.exists(filename):
         raise FileNotFoundError(f"No checkpoint found at {filename}")
     checkpoint = torch.load(filename, map_location="cpu", weights_only=False)
-    model.load_state_dict(checkpoint.pop("model_state_dict"))
+    weights = checkpoint.pop("model_state_dict")
+    averaged = checkpoint.pop("vcg_ema", None)
+    if ema:
+        if averaged is None:
+            raise KeyError(f"{filename} holds no averaged weights (vcg_ema): it was trained without --ema_decay")
+        unknown = sorted(set(averaged["state_dict"]) - set(weights))
+        if unknown:
+            raise KeyError(f"{filename}: averaged weights for parameters the model state does not have: {unknown[:3]}")
+        weights = dict(weights, **averaged["state_dict"])
+    model.load_state_dict(weights)
     ops.PARAM_EPOCH[0] += 1                              # load_state_dict wrote through .data: drop every weight pack
     checkpoint.pop("optimizer_states", None)
     return checkpoint
