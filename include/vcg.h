@@ -386,6 +386,26 @@ int vcg_ema_update(float* e, const float* p, size_t n, float w, const float* ski
    [a, a + n) and [b, b + n) that overlap.  n == 0 is a no-op. */
 int vcg_swap(float* a, float* b, size_t n, void* stream);
 
+/* Image history pool of the discriminators (new: replaces nothing in the reference, which trains its discriminators on the fakes
+   of the current step only) — csrc/image_pool.hip -------------------------------------------------------------------------------
+   The buffer of Shrivastava et al., "Learning from Simulated and Unsupervised Images through Adversarial Training" (CVPR 2017),
+   as CycleGAN-style trainers use it: the discriminator is shown each new fake either as itself or exchanged against a stored one.
+   fake, out: N images of elems contiguous floats each (any layout: the call is geometry-blind); pool: capacity slots of elems
+   floats.  plan: N entries in HOST memory, read before the call returns and applied in order n = 0 .. N-1:
+     -1                     keep:   out[n] = fake[n]
+     s in [0, capacity)     swap:   out[n] = pool[s], then pool[s] = fake[n]
+     -(2 + s)               store:  pool[s] = fake[n], out[n] = fake[n]; the slot's old content is not read (it may be uninitialised)
+   Two entries may name one slot: the later one receives what the earlier one put there, and the slot ends up with the later fake.
+   The plan travels in the kernel arguments, 64 entries per launch: nothing is uploaded or synchronised; N > 64 is several launches
+   on `stream`.  A lane owns one element index and walks the samples in order, so a slot written and read again within a call is
+   written and read by one lane.  Data moves as 32-bit words (a NaN keeps its payload); fake is read only; slots the plan does not
+   name keep their bits.  Vector loads and stores only, no atomics, no workspace.
+   Refused (non-zero, vcg_last_error, nothing launched): a null pointer; fake, pool or out not 16-byte aligned; N < 0;
+   capacity < 1; elems == 0 with N > 0; a plan entry outside the three forms; any overlap between the ranges fake[N * elems],
+   out[N * elems] and pool[capacity * elems].  N == 0 is a no-op. */
+int vcg_pool_exchange(const float* fake, float* pool, float* out, const int32_t* plan, int N, size_t elems, int capacity,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

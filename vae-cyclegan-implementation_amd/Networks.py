@@ -21,6 +21,7 @@ from torch.nn.utils import spectral_norm
 from . import ops
 from .Losses import (CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss, StructuralLoss,
                      KLDivergenceLoss, TranslationLoss)
+from .image_pool import ImagePool, pool_seed as _pool_seed
 from .optim import FusedAdam
 
 _ACTS = {"ReLU": ops.ACT_RELU, "LeakyReLU": ops.ACT_LEAKY, "Identity": ops.ACT_NONE, "Tanh": ops.ACT_TANH, "Sigmoid": ops.ACT_SIGMOID}
@@ -300,6 +301,71 @@ def _ema_decay(ema_decay):
     return None if d == 0.0 else d
 
 
+def _pool_size(pool_size):
+    """configure_optimizers(pool_size=n) -> the capacity of each discriminator's image history pool: an integer >= 0, 0 is off (no
+    pool object exists and the step allocates, launches and draws nothing new)."""
+    if isinstance(pool_size, bool) or int(pool_size) != pool_size or int(pool_size) < 0:
+        raise ValueError(f"pool_size must be an integer >= 0 (0 switches the image history pool off), got {pool_size!r}")
+    return int(pool_size)
+
+
+def _refuse_pool(model, pool_size):
+    """The models without a discriminator take the keyword so that one call fits every architecture: 0 is ignored."""
+    if _pool_size(pool_size) != 0:
+        raise ValueError(f"pool_size={pool_size}: {type(model).__name__} has no discriminator to keep an image history pool for "
+                         "(cyclevaegan, cycleaegan, aegan and vaegan have)")
+
+
+class _PoolMixin:
+    """Image history pools (image_pool.ImagePool) of a model whose configure_optimizers was given pool_size > 0: one per
+    discriminator, under the discriminator's attribute name.  `image_pools` is None otherwise.
+
+    The step with pools: forward and the shared discriminator pass as without (the G phase is untouched), then each pool exchanges
+    its discriminator's fakes on the main stream.  A discriminator whose plan was an identity (keeps and stores only: the whole
+    filling phase) takes its weight gradients from the shared pass, exactly the step without a pool.  Otherwise its fake term
+    comes from one more ordinary call D(pooled) on the whole batch, after the fake and the real call of the shared pass (spectral
+    norm's power iteration advances per call), and the shared pass still provides the real term.
+
+    Under data parallelism the ranks draw different plans, and a discriminator's backward nodes run in another order with the
+    extra call than without it, so the order in which gradient buckets complete would differ between ranks: there every rank takes
+    the extra call whenever its pool drew at all (`last_drew`: the pool is full — the same steps on every rank, their shards being
+    equal), kept samples included."""
+    image_pools = None
+    debug_mode = False
+
+    def _make_pools(self, names, pool_size, pool_seed):
+        size = _pool_size(pool_size)
+        self.image_pools = {n: ImagePool(size, _pool_seed(pool_seed, i)) for i, n in enumerate(names)} if size else None
+
+    @property
+    def pool_enabled(self):
+        return bool(self.image_pools)
+
+    def _shown_to(self, name, fake):
+        """(pooled batch, whether discriminator `name` needs the extra call on it) for this step's `fake`."""
+        pool = self.image_pools[name]
+        shown = pool.exchange(fake)
+        extra = pool.last_drew if self.grad_reducer is not None else not pool.last_identity
+        return shown, extra
+
+    def _debug_store(self):
+        return self.__dict__.setdefault("debug_info", {})
+
+    def save_pool_state(self):
+        """{discriminator name: ImagePool.state_dict()} — what a checkpoint stores under `vcg_image_pool`."""
+        if not self.image_pools:
+            raise RuntimeError("save_pool_state(): this model keeps no image history pool (configure_optimizers(pool_size=...))")
+        return {n: p.state_dict() for n, p in self.image_pools.items()}
+
+    def load_pool_state(self, state, device=None):
+        if not self.image_pools:
+            raise RuntimeError("load_pool_state(): this model keeps no image history pool (configure_optimizers(pool_size=...))")
+        if set(state) != set(self.image_pools):
+            raise KeyError(f"saved image pools {sorted(state)} do not match this model's {sorted(self.image_pools)}")
+        for n, p in self.image_pools.items():
+            p.load_state_dict(state[n], device=device)
+
+
 def _clip_scalars(**optimizers):
     """{suffix: optimizer} -> the device scalars a clipping optimizer's last step left in `clip_state`, under the metric names
     grad_norm<suffix> / grad_skipped<suffix> ("" for the one-optimizer models, "_G" / "_D" otherwise); {} when clipping is off.
@@ -451,7 +517,8 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
     def forward(self, x):
         return self.decoder(self.encoder(x))
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), decoder_only=False, clip_grad_norm=0.0, ema_decay=0.0):
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), decoder_only=False, clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
+        _refuse_pool(self, pool_size)
         params = self.decoder.parameters() if decoder_only else self.parameters()
         self.optimizer = FusedAdam(params, lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
                                    ema_decay=_ema_decay(ema_decay))
@@ -548,7 +615,8 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         Gx = self.decoder(self.variational_decoder_block(z))
         return Gx, mu, logvar
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
+        _refuse_pool(self, pool_size)
         self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
                                    ema_decay=_ema_decay(ema_decay))
         return self.optimizer
@@ -640,7 +708,7 @@ def _ae_pair(ae_a, a, ae_b, b, fork):
     return ra, rb
 
 
-class CycleVAEGAN(_EmaMixin, nn.Module):
+class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
     """Two VAEs (G: X->Y, F: Y->X) + two discriminators; cycle + LSGAN + KL (+identity if paired);
     alternating G then D update  (reference Networks.py:1872-2150).
 
@@ -696,7 +764,10 @@ class CycleVAEGAN(_EmaMixin, nn.Module):
         return (Gx, FGx, Fy, GFy, mu_x, logvar_x, mu_FGx, logvar_FGx, mu_y, logvar_y, mu_GFy, logvar_GFy,
                 DYGx, DXFy, DXx, DYy, Gy, Fx)
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0, pool_seed=0):
+        # pool_size > 0: an image history pool of that many images per discriminator (DX pools F(y), DY pools G(x)), their plans
+        # drawn from generators seeded from pool_seed (_PoolMixin)
+        self._make_pools(("DX", "DY"), pool_size, pool_seed)
         # one bound, two norms: the generators' and the discriminators' gradients are clipped each by their own
         bound = _max_grad_norm(clip_grad_norm)
         self.optimizer_G = FusedAdam(list(self.F.parameters()) + list(self.G.parameters()), lr=lr, betas=betas, max_grad_norm=bound,
@@ -842,6 +913,23 @@ class CycleVAEGAN(_EmaMixin, nn.Module):
         out.update(host)
         return out
 
+    def _pooled_d_terms(self, t, Gx, Fy):
+        """The discriminators' fake terms with image history pools (_PoolMixin), after the forward (both direction streams are
+        joined by then) on the main stream.  Replaces D_loss_x_fake / D_loss_y_fake and D_loss in `t` for the discriminators whose
+        batch was exchanged; G_loss and everything the G phase differentiates stay the shared pass's."""
+        fake_x, fake_y = Fy.detach(), Gx.detach()
+        shown_x, extra_x = self._shown_to("DX", fake_x)
+        shown_y, extra_y = self._shown_to("DY", fake_y)
+        if extra_x:
+            t["D_loss_x_fake"], _ = ops.mse_const(self.DX(shown_x), 0.0)
+        if extra_y:
+            t["D_loss_y_fake"], _ = ops.mse_const(self.DY(shown_y), 0.0)
+        if extra_x or extra_y:
+            t["D_loss"] = ops.weighted_sum([t["D_loss_x_real"], t["D_loss_x_fake"], t["D_loss_y_real"], t["D_loss_y_fake"]],
+                                           [1.0] * 4)
+        if self.debug_mode:
+            self._debug_store().update(fake_x=fake_x, fake_y=fake_y, d_fake_x=shown_x, d_fake_y=shown_y)
+
     def training_step(self, batch):
         _refuse_training_in_ema_scope(self)
         self._check_configured()
@@ -851,7 +939,9 @@ class CycleVAEGAN(_EmaMixin, nn.Module):
 
         red = self.grad_reducer
         self.optimizer_G.zero_grad()
-        t, _, _ = self._generator_losses(x, y, two_streams=ops.two_directions())
+        t, Gx, Fy = self._generator_losses(x, y, two_streams=ops.two_directions())
+        if self.image_pools:
+            self._pooled_d_terms(t, Gx, Fy)
         if red is not None:
             red.begin(self.optimizer_G)          # F+G buckets are all-reduced from inside the backward as they complete
         # generator gradients reach F and G only (the discriminators contribute their data gradient)
@@ -1014,7 +1104,8 @@ class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
         self.lambda_cycle = 0
         self.lambda_kl = 0
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
+        _refuse_pool(self, pool_size)
         self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
                                    ema_decay=_ema_decay(ema_decay))
         return self.optimizer
@@ -1199,7 +1290,8 @@ class DoubleAutoencoder(_OptimizerStatesMixin, nn.Module):
         cycle_ae.F.decoder.load_state_dict(self.decoder_A.state_dict())
         return cycle_ae
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
+        _refuse_pool(self, pool_size)
         self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
                                    ema_decay=_ema_decay(ema_decay))
         return self.optimizer
@@ -1309,7 +1401,8 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             gen.decoder.load_state_dict(getattr(self, "decoder_" + sfx).state_dict())
         return cycle_vae
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
+        _refuse_pool(self, pool_size)
         self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
                                    ema_decay=_ema_decay(ema_decay))
         return self.optimizer
@@ -1354,14 +1447,15 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
                     "loss_kl_B": h["loss_kl_B"], "Gx": self.translate_A_to_B(x), "Fy": self.translate_B_to_A(y)}
 
 
-class _SingleGAN(_EmaMixin, nn.Module):
+class _SingleGAN(_PoolMixin, _EmaMixin, nn.Module):
     """One generator G: X->Y and one discriminator D on Y, alternating G / D updates — the shared step of AEGAN and VAEGAN
     (reference Networks.py:991-1348).  As in CycleVAEGAN the discriminator runs once per step: the G phase takes its data
     gradient, the D phase its weight gradients from the same activations.  VAEGAN is written that way in the reference
     (`DGx.detach()`, `retain_graph`, :1277-1287); AEGAN re-runs D on the detached G(x) after the generator update
     (:1105-1108), which reproduces the same outputs because that update does not touch D."""
 
-    def configure_optimizers(self, lr=2e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0):
+    def configure_optimizers(self, lr=2e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0, pool_seed=0):
+        self._make_pools(("D",), pool_size, pool_seed)    # pool_size > 0: D's image history pool of G(x) (_PoolMixin)
         bound = _max_grad_norm(clip_grad_norm)            # one bound, two norms (CycleVAEGAN.configure_optimizers)
         self.optimizer_G = FusedAdam(self.G.parameters(), lr=lr, betas=betas, max_grad_norm=bound, ema_decay=_ema_decay(ema_decay))
         self.optimizer_D = FusedAdam(self.D.parameters(), lr=lr, betas=betas, max_grad_norm=bound)
@@ -1390,6 +1484,17 @@ class _SingleGAN(_EmaMixin, nn.Module):
         t["D_loss_real"], _ = ops.mse_const(Dy, 1.0)
         t["D_loss_fake"], _ = ops.mse_const(DGx, 0.0)
         t["D_loss"] = ops.weighted_sum([t["D_loss_real"], t["D_loss_fake"]], [1.0, 1.0])
+
+    def _pooled_d_terms(self, t, Gx):
+        """D's fake term with an image history pool (_PoolMixin; CycleVAEGAN._pooled_d_terms).  VAEGAN's D_loss_backward stays the
+        real term: its fake term is a constant of the backward with or without a pool."""
+        fake = Gx.detach()
+        shown, extra = self._shown_to("D", fake)
+        if extra:
+            t["D_loss_fake"], _ = ops.mse_const(self.D(shown), 0.0)
+            t["D_loss"] = ops.weighted_sum([t["D_loss_real"], t["D_loss_fake"]], [1.0, 1.0])
+        if self.debug_mode:
+            self._debug_store().update(fake=fake, d_fake=shown)
 
     def _alternating_step(self, t):
         g_params, d_params = self.optimizer_G.params, self.optimizer_D.params
@@ -1474,7 +1579,9 @@ class AEGAN(_SingleGAN):
     def training_step(self, batch):
         _refuse_training_in_ema_scope(self)
         self._check_configured()
-        t, _ = self._losses(batch)
+        t, Gx = self._losses(batch)
+        if self.image_pools:
+            self._pooled_d_terms(t, Gx)
         self._alternating_step(t)
         clip = _clip_scalars(_G=self.optimizer_G, _D=self.optimizer_D)
         h = _metrics_to_host(dict(t, **clip), self.grad_reducer)
@@ -1548,7 +1655,9 @@ class VAEGAN(_SingleGAN):
         _refuse_training_in_ema_scope(self)
         if self.optimizer_G is None or self.optimizer_D is None:
             raise ValueError("Optimizers have not been configured yet.")
-        t, _ = self._losses(batch)
+        t, Gx = self._losses(batch)
+        if self.image_pools:
+            self._pooled_d_terms(t, Gx)
         self._alternating_step(t)
         clip = _clip_scalars(_G=self.optimizer_G, _D=self.optimizer_D)
         h = _metrics_to_host(dict(t, **clip), self.grad_reducer)

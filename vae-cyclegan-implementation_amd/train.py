@@ -206,6 +206,20 @@ def ema_decay_value(text):
     return value
 
 
+POOL_ARCHS = ("aegan", "vaegan", "cycleaegan", "cyclevaegan")       # the architectures with a discriminator
+
+
+def pool_size_value(text):
+    """argparse type of --pool_size: an integer >= 0 (0: off)."""
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+    if value < 0:
+        raise argparse.ArgumentTypeError(f"--pool_size must be an integer >= 0 (0 switches the image history pool off), got {text}")
+    return value
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="Train VAE-CycleGAN models (MI355X-native path)")
     p.add_argument("--architecture", type=str, default="autoencoder", choices=REFERENCE_ARCHS + list(ALIASES))
@@ -236,6 +250,10 @@ def build_parser():
                    help="keep an exponential moving average of the generator weights with this decay (e.g. 0.999, warmed up from "
                         "the first step); the test loss that selects best_model.pth is then the averaged weights', and test.py / "
                         "translate.py --ema load them; 0: off")
+    p.add_argument("--pool_size", type=pool_size_value, default=0,
+                   help="image history pool of this many generated images per discriminator (" + ", ".join(POOL_ARCHS) + "): each "
+                        "fake is shown to its discriminator as itself or, half of the time once the pool is full, exchanged "
+                        "against a random stored one; 50 is the customary value; 0: off")
     p.add_argument("--output_dir", type=str, default="runs")
     p.add_argument("--save_freq", type=int, default=10)
     p.add_argument("--log_image_freq", type=int, default=5)
@@ -316,6 +334,12 @@ def main(args):
     ema_decay = getattr(args, "ema_decay", 0.0)
     if not math.isfinite(ema_decay) or not 0.0 <= ema_decay < 1.0:
         raise ValueError(f"--ema_decay must be finite and lie in [0, 1) (0 switches the averaged weights off), got {ema_decay}")
+    pool_size = getattr(args, "pool_size", 0)
+    if isinstance(pool_size, bool) or not isinstance(pool_size, int) or pool_size < 0:
+        raise ValueError(f"--pool_size must be an integer >= 0 (0 switches the image history pool off), got {pool_size}")
+    if pool_size > 0 and args.architecture not in POOL_ARCHS:
+        raise ValueError(f"--pool_size is supported by {', '.join(POOL_ARCHS)} only: {args.architecture} has no discriminator, "
+                         "the flag would be ignored")
     # reference train.py:362-377, in its order: the autoencoder / VAE check sees the modalities as given, THEN the
     # per-dataset defaults fill in what was not given (they name the run directory and select hypersim's frames)
     if args.architecture in ("autoencoder", "vae"):
@@ -361,7 +385,13 @@ def main(args):
     torch.manual_seed(args.seed)                     # identical replicas
     ops.manual_seed(ops.rank_seed(args.seed, rank))  # per-rank eps stream
     model = create_model(args.architecture, paired=args.paired, latent_dim=args.latent_dim).to(device)
-    model.configure_optimizers(lr=args.lr, clip_grad_norm=clip, ema_decay=ema_decay)
+    if pool_size > 0:                                # the pools draw their plans per rank, as the eps streams do
+        model.configure_optimizers(lr=args.lr, clip_grad_norm=clip, ema_decay=ema_decay, pool_size=pool_size,
+                                   pool_seed=ops.rank_seed(args.seed, rank))
+        if rank == 0:
+            print(f"Image history pool: {pool_size} images per discriminator")
+    else:
+        model.configure_optimizers(lr=args.lr, clip_grad_norm=clip, ema_decay=ema_decay)
     if ema_decay > 0.0 and rank == 0:
         print(f"Averaged generator weights (decay {ema_decay}): the test loss, and with it best_model.pth, is the averaged weights'")
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
@@ -424,7 +454,8 @@ def main(args):
                     print(f"  {k}: {v:.6f}")
                 if test_loss < best_test_loss:       # reference train.py:565-570
                     best_test_loss = test_loss
-                    utils.save_checkpoint(model, epoch, test_loss, args, output_dir / "best_model.pth", best_test_loss)
+                    utils.save_checkpoint(model, epoch, test_loss, args, output_dir / "best_model.pth", best_test_loss,
+                                          pool_images=False)
                     print(f"New best model saved (test_loss: {test_loss:.4f})")
         if rank == 0 and (epoch + 1) % args.save_freq == 0:      # reference train.py:573-575 (replicas are identical)
             utils.save_checkpoint(model, epoch, train_loss, args, output_dir / f"checkpoint_epoch_{epoch + 1}.pth", best_test_loss)

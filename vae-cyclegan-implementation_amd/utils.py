@@ -29,7 +29,27 @@ def _rank():
     return int(os.environ.get("RANK", "0"))
 
 
-def save_checkpoint(model, epoch, loss, args, filename, best_test_loss=None):
+def _world():
+    try:
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_world_size()
+    except Exception:
+        pass
+    return int(os.environ.get("WORLD_SIZE", "1"))
+
+
+_POOLS_NOT_SAVED = [False]      # the one-time notice of a data-parallel run with image history pools
+
+
+def _tell_pools_are_per_rank():
+    if not _POOLS_NOT_SAVED[0] and _rank() == 0:
+        print("Image history pools are per rank: with more than one rank they are not written to checkpoints, and a resumed run "
+              "starts every rank with empty pools")
+    _POOLS_NOT_SAVED[0] = True
+
+
+def save_checkpoint(model, epoch, loss, args, filename, best_test_loss=None, pool_images=True):
     """reference utils.py:17-28.  Tensors are written from the CPU so the file loads on a machine without a GPU
     (the reference's own loader passes map_location anyway).  Two keys are ADDED to the reference's five (its loader
     reads the ones it knows and ignores the rest): the position of the on-device eps stream (`vcg_eps_rng`) so that a
@@ -44,7 +64,13 @@ def save_checkpoint(model, epoch, loss, args, filename, best_test_loss=None):
     A model that keeps averaged generator weights (configure_optimizers(ema_decay=...)) adds a third key, `vcg_ema` =
     {"decay", "updates", "state_dict"}: the average under state_dict()'s names, for the tracked parameters only.  It is absent
     otherwise, and `model_state_dict` is the raw weights either way: a resumed run continues from what it trained, and the
-    reference's loader reads the file as before."""
+    reference's loader reads the file as before.
+
+    A single-process model that keeps image history pools (configure_optimizers(pool_size=...)) adds `vcg_image_pool` =
+    {discriminator name: ImagePool.state_dict()}: count, image shape, the plan generator's state and the stored images, so that
+    a resumed run shows its discriminators what the uninterrupted run would have.  `pool_images=False` leaves the key out
+    (best_model.pth: a file to evaluate, not to resume).  With more than one rank every rank owns different pools and one rank
+    writes the file: the key is left out, and a resumed run starts with empty pools on every rank."""
     rank = _rank()
     seed = int(ops._RNG["seed"])
     checkpoint = {
@@ -59,6 +85,11 @@ def save_checkpoint(model, epoch, loss, args, filename, best_test_loss=None):
         checkpoint["vcg_best_test_loss"] = float(best_test_loss)
     if getattr(model, "ema_enabled", False):
         checkpoint["vcg_ema"] = _to_cpu(model.save_ema_state())
+    if getattr(model, "pool_enabled", False) and pool_images:
+        if _world() > 1:
+            _tell_pools_are_per_rank()
+        else:
+            checkpoint["vcg_image_pool"] = model.save_pool_state()
     torch.save(checkpoint, filename)
     print(f"Checkpoint saved to {filename}")
 
@@ -93,6 +124,13 @@ def load_checkpoint(model, filename, device):
             model.load_ema_state(checkpoint["vcg_ema"])
         else:
             print(f"{filename} holds no averaged weights: the average starts from the loaded weights")
+    if getattr(model, "pool_enabled", False):            # (a `vcg_image_pool` key in the file of a run without pools is ignored)
+        if _world() > 1:
+            _tell_pools_are_per_rank()
+        elif "vcg_image_pool" in checkpoint:
+            model.load_pool_state(checkpoint["vcg_image_pool"], device=device)
+        else:
+            print(f"{filename} holds no image history pools: they start empty")
     ops.PARAM_EPOCH[0] += 1                              # load_state_dict wrote through .data: drop every weight pack
     epoch, loss = checkpoint["epoch"], checkpoint["loss"]
     print(f"Loaded checkpoint from {filename} (epoch {epoch}, loss {loss:.4f})")
