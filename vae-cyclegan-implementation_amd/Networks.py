@@ -474,7 +474,15 @@ class _EmaMixin:
 
 
 class _OptimizerStatesMixin(_EmaMixin):
+    """The optimizers of a model, by attribute name: one `optimizer`, or `optimizer_G` / `optimizer_D` (_GanMixin)."""
     _opt_names = ("optimizer",)
+
+    def _single_optimizer(self, params, lr, betas, clip_grad_norm, ema_decay, pool_size):
+        """configure_optimizers of the models with one Adam and no discriminator."""
+        _refuse_pool(self, pool_size)
+        self.optimizer = FusedAdam(params, lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
+                                   ema_decay=_ema_decay(ema_decay))
+        return self.optimizer
 
     def save_optimizer_states(self):
         out = {}
@@ -495,6 +503,80 @@ class _OptimizerStatesMixin(_EmaMixin):
             if name not in states:
                 raise KeyError(f"{name} state not found in states")
             getattr(self, name).load_state_dict(states[name])
+
+
+class _GanMixin(_PoolMixin, _OptimizerStatesMixin):
+    """The models with discriminators (`_discriminators`, trained by optimizer_D) beside their generators (`_generators`,
+    optimizer_G): the optimizer pair and the alternating G then D update."""
+    _opt_names = ("optimizer_G", "optimizer_D")
+
+    def _gan_optimizers(self, lr, betas, clip_grad_norm, ema_decay, pool_size, pool_seed):
+        # pool_size > 0: an image history pool of that many images per discriminator (DX pools F(y), DY pools G(x), D pools G(x)),
+        # their plans drawn from generators seeded from pool_seed (_PoolMixin)
+        self._make_pools(self._discriminators, pool_size, pool_seed)
+        # one bound, two norms: the generators' and the discriminators' gradients are clipped each by their own
+        bound = _max_grad_norm(clip_grad_norm)
+        g_params, d_params = ([p for n in names for p in getattr(self, n).parameters()]
+                              for names in (self._generators, self._discriminators))
+        self.optimizer_G = FusedAdam(g_params, lr=lr, betas=betas, max_grad_norm=bound,
+                                     ema_decay=_ema_decay(ema_decay))            # the generators' average; none for discriminators
+        self.optimizer_D = FusedAdam(d_params, lr=lr, betas=betas, max_grad_norm=bound)
+        return self.optimizer_G, self.optimizer_D
+
+    def _alternating_step(self, G_loss, D_loss):
+        """Both updates from one forward, whose caller zeroed optimizer_G's gradients before it: the G-phase backward takes only
+        the discriminators' data gradient, the D-phase backward their weight gradients from the same saved activations."""
+        opt_G, opt_D, red = self.optimizer_G, self.optimizer_D, self.grad_reducer
+        if red is not None:
+            red.begin(opt_G)                     # generator buckets are all-reduced from inside the backward as they complete
+        # generator gradients reach the generators only (the discriminators contribute their data gradient)
+        with ops.no_wgrad(opt_D.params):
+            ops.backward_overlapped(G_loss, inputs=opt_G.params, retain_graph=True)
+        if red is not None:
+            red.start(opt_G)                     # whatever is left; it runs under the D backward below
+        # discriminator gradients from the same activations reach the discriminators only — what detaching G(x), F(y) achieves
+        # in the reference (:2028-2029).  Neither this backward nor D_loss reads a generator parameter, so running it before
+        # optimizer_G.step() changes nothing.
+        opt_D.zero_grad()
+        if red is not None:
+            red.begin(opt_D)
+        with ops.no_dgrad([getattr(self, n).model[0]._spec for n in self._discriminators]):
+            ops.backward_overlapped(D_loss, inputs=opt_D.params)
+        if red is not None:
+            red.start(opt_D)
+            red.finish(opt_G)
+        opt_G.step()
+        if red is not None:
+            red.finish(opt_D)
+        opt_D.step()
+
+
+def _same(*names):
+    """_report entries reported under their source's own name."""
+    return tuple((n, n) for n in names)
+
+
+_GX, _GX_FY = (("Gx", None),), (("Gx", None), ("Fy", None))      # validation's translated batches (_report's `images`)
+
+
+def _report(model, t, spec, training, **images):
+    """What a step returns.  `spec`: the model's ordered (reported name, source) pairs — a source is a key of the step's device
+    scalars `t`, a pair of keys (their sum on the host: total_loss = G_loss + D_loss) or None (the entry of `images`).  All
+    sources and, after a training step, what the optimizer steps left on the device (_clip_scalars) cross in ONE device->host
+    copy, averaged over ranks when training; the clip keys follow the model's own.  A new step-level metric is added here,
+    once."""
+    clip = _clip_scalars(**{n[len("optimizer"):]: getattr(model, n) for n in model._opt_names}) if training else {}
+    named = {}
+    for _, src in spec:
+        for s in (src,) if isinstance(src, str) else src or ():
+            named[s] = t[s]
+    named.update(clip)
+    host = _metrics_to_host(named, model.grad_reducer if training else None)
+    out = {}
+    for name, src in spec:
+        out[name] = images[name] if src is None else host[src] if isinstance(src, str) else host[src[0]] + host[src[1]]
+    out.update({k: host[k] for k in clip})
+    return out
 
 
 class Autoencoder(_OptimizerStatesMixin, nn.Module):
@@ -518,17 +600,16 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         return self.decoder(self.encoder(x))
 
     def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), decoder_only=False, clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
-        _refuse_pool(self, pool_size)
         params = self.decoder.parameters() if decoder_only else self.parameters()
-        self.optimizer = FusedAdam(params, lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
-                                   ema_decay=_ema_decay(ema_decay))
-        return self.optimizer
+        return self._single_optimizer(params, lr, betas, clip_grad_norm, ema_decay, pool_size)
 
     def configure_loss(self, **kwargs):
         self.loss_fn = TranslationLoss()
         self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
 
     def training_step(self, batch):
+        """Written out (no _report): the reference's NaN / Inf guard reads the loss on the host before the update, and the plain
+        step reuses that value instead of a second copy."""
         _refuse_training_in_ema_scope(self)
         if self.loss_fn is None:
             raise ValueError("Loss function has not been configured yet.")
@@ -580,10 +661,10 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
             output = self(x)
             if self.loss_ssim_fn is not None:
                 loss_trans, loss_ssim = self.loss_fn(output, y), self.loss_ssim_fn(output, y)
-                m = _metrics_to_host({"G_loss": ops.weighted_sum([loss_trans, loss_ssim], [1.0, self.lambda_ssim]),
-                                      "loss_trans": loss_trans, "loss_ssim": loss_ssim})
-                return {"G_loss": m["G_loss"], "total_loss": m["G_loss"], "loss_trans": m["loss_trans"],
-                        "loss_ssim": m["loss_ssim"], "Gx": output}
+                t = {"G_loss": ops.weighted_sum([loss_trans, loss_ssim], [1.0, self.lambda_ssim]), "loss_trans": loss_trans,
+                     "loss_ssim": loss_ssim}
+                return _report(self, t, (("G_loss", "G_loss"), ("total_loss", "G_loss")) + _same("loss_trans", "loss_ssim") + _GX,
+                               False, Gx=output)
             value = float(self.loss_fn(output, y))
             return {"G_loss": value, "total_loss": value, "loss_trans": value, "Gx": output}
 
@@ -616,10 +697,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         return Gx, mu, logvar
 
     def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
-        _refuse_pool(self, pool_size)
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
-                                   ema_decay=_ema_decay(ema_decay))
-        return self.optimizer
+        return self._single_optimizer(self.parameters(), lr, betas, clip_grad_norm, ema_decay, pool_size)
 
     def configure_loss(self, **kwargs):
         self.loss_trans_fn = TranslationLoss()
@@ -636,6 +714,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             raise ValueError("KL divergence loss function has not been configured yet.")
 
     def _losses(self, batch):
+        """-> (G(x), the step's scalars in the order they are reported: G_loss, loss_trans, loss_kl, [loss_ssim])"""
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         output, mu, logvar = self(x)
         loss_trans = self.loss_trans_fn(output, y)
@@ -654,18 +733,16 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self._check_configured()
         _, named = self._losses(batch)
         _backward_and_step(named["G_loss"], self.optimizer, self.grad_reducer)
-        named.update(_clip_scalars(**{"": self.optimizer}))
-        return _metrics_to_host(named, self.grad_reducer)
+        return _report(self, named, _same(*named), True)
 
     def validation_step(self, batch):
         self._check_configured()
         with torch.no_grad():
             output, named = self._losses(batch)
-            m = _metrics_to_host(named)
-            m["Gx"] = output
-            return m
+            return _report(self, named, _same(*named) + _GX, False, Gx=output)
 
 
+# --------------------------------------------------------------------------- the two translation directions
 def _vae_pair(vae_a, a, ticket_a, vae_b, b, ticket_b, fork):
     """vae_a(a) on the caller's stream and vae_b(b) on `fork`'s second stream, issued alternately in half-generator pieces
     (encoder | bottleneck + decoder): the second stream has work after a quarter of the host time a whole generator takes to
@@ -708,7 +785,66 @@ def _ae_pair(ae_a, a, ae_b, b, fork):
     return ra, rb
 
 
-class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
+def _fork(x, y):
+    """Open the second stream for a step over `x` and `y` (ops.DirectionFork; the caller joins it).  Both inputs' magnitudes are
+    published first: a tensor that two streams will read must not be measured by one of them after they have forked."""
+    ops.premeasure(x)
+    ops.premeasure(y)
+    return ops.DirectionFork(x.device)
+
+
+def _eps_shape(vae, x):
+    """Shape of the eps one forward of `vae` on `x` draws."""
+    n, _, h, w = x.shape
+    return (n, vae.variational_encoder_block.latent_dim, h // 16, w // 16)
+
+
+def _two_directions(G, F, x, y, fork=None, tickets=None, identity=None):
+    """x -> G -> F and y -> F -> G for two autoencoders or two VAEs -> ((G(x), F(G(x)), F(y), G(F(y))), their (mu, logvar)s
+    flattened in that order — empty for autoencoders —, G(y), F(x)).
+
+    With a `fork`: x -> G -> F on the caller's stream and y -> F -> G on the second one, issued interleaved (_vae_pair) so that
+    both have work from the start.  Same results bit for bit: VAEs draw at `tickets`, the positions of those four calls reserved
+    in the reference's call order.  Without: the four calls in the reference's order on one stream; `identity(generator,
+    image)`, if given, is called for G(y) after G(x) and for F(x) after F(y) — where the reference's CycleVAEGAN computes (and
+    draws eps for) the identity passes — and G(y), F(x) are what it returns (None otherwise)."""
+    Gy = Fx = None
+    if fork is None:
+        rGx = G(x)
+        if identity is not None:
+            Gy = identity(G, y)
+        rFGx = F(rGx[0] if isinstance(rGx, tuple) else rGx)
+        rFy = F(y)
+        if identity is not None:
+            Fx = identity(F, x)
+        rGFy = G(rFy[0] if isinstance(rFy, tuple) else rFy)
+    elif tickets is None:
+        rGx, rFy = _ae_pair(G, x, F, y, fork)
+        rFGx, rGFy = _ae_pair(F, rGx, G, rFy, fork)
+    else:
+        rGx, rFy = _vae_pair(G, x, tickets[0], F, y, tickets[2], fork)
+        rFGx, rGFy = _vae_pair(F, rGx[0], tickets[1], G, rFy[0], tickets[3], fork)
+    rs = (rGx, rFGx, rFy, rGFy)
+    if isinstance(rGx, tuple):                   # VariationalAutoencoder.forward: (image, mu, logvar)
+        return tuple(r[0] for r in rs), tuple(s for r in rs for s in r[1:]), Gy, Fx
+    return rs, (), Gy, Fx
+
+
+def _discriminate(DY, DX, Gx, Fy, x, y, fork=None):
+    """-> DY(G(x)), DX(F(y)), DX(x), DY(y), issued DY(G(x)), DX(F(y)), DY(y), DX(x): alternately on the two streams of `fork`
+    (32.64 -> 32.42 ms over three A/B pairs), each discriminator seeing its fake before its real batch as in the reference
+    (spectral norm's power iteration advances per call)."""
+    second = fork.second if fork is not None else contextlib.nullcontext
+    DYGx = DY(Gx)
+    with second():
+        DXFy = DX(Fy)
+    DYy = DY(y)
+    with second():
+        DXx = DX(x)
+    return DYGx, DXFy, DXx, DYy
+
+
+class CycleVAEGAN(_GanMixin, nn.Module):
     """Two VAEs (G: X->Y, F: Y->X) + two discriminators; cycle + LSGAN + KL (+identity if paired);
     alternating G then D update  (reference Networks.py:1872-2150).
 
@@ -720,11 +856,14 @@ class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
         (the reference recomputes four D forwards at :2032-2035 with unchanged D weights, and
         discards the D weight gradients of its G-phase backward at :2025).
     """
+    _generators, _discriminators = ("F", "G"), ("DX", "DY")
+    _variational = True                          # CycleAEGAN: plain autoencoders — no eps, no KL term
+    _GAN_G_TERMS = ("loss_gan_g_x_fake", "loss_gan_g_y_fake")        # what G_loss takes of the LSGAN generator loss
 
     def __init__(self, latent_dim=64, paired=True):
         super().__init__()
-        self.F = VariationalAutoencoder(latent_dim)
-        self.G = VariationalAutoencoder(latent_dim)
+        self.F = self._make_generator(latent_dim)
+        self.G = self._make_generator(latent_dim)
         self.DX = Discriminator()
         self.DY = Discriminator()
         self.paired = paired
@@ -742,6 +881,9 @@ class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
         self.lambda_ssim = 0.0
         # data-parallel hook: set by parallel.attach(); called as reducer(phase, optimizer)
         self.grad_reducer = None
+
+    def _make_generator(self, latent_dim):
+        return VariationalAutoencoder(latent_dim)
 
     def _init_weights(self, module):
         _kaiming_relu_init(module)
@@ -765,29 +907,7 @@ class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
                 DYGx, DXFy, DXx, DYy, Gy, Fx)
 
     def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0, pool_seed=0):
-        # pool_size > 0: an image history pool of that many images per discriminator (DX pools F(y), DY pools G(x)), their plans
-        # drawn from generators seeded from pool_seed (_PoolMixin)
-        self._make_pools(("DX", "DY"), pool_size, pool_seed)
-        # one bound, two norms: the generators' and the discriminators' gradients are clipped each by their own
-        bound = _max_grad_norm(clip_grad_norm)
-        self.optimizer_G = FusedAdam(list(self.F.parameters()) + list(self.G.parameters()), lr=lr, betas=betas, max_grad_norm=bound,
-                                     ema_decay=_ema_decay(ema_decay))            # the generators' average; none for DX, DY
-        self.optimizer_D = FusedAdam(list(self.DX.parameters()) + list(self.DY.parameters()), lr=lr, betas=betas, max_grad_norm=bound)
-        return self.optimizer_G, self.optimizer_D
-
-    def save_optimizer_states(self):
-        if self.optimizer_G is None or self.optimizer_D is None:
-            raise ValueError("Optimizers have not been configured yet.")
-        return {"optimizer_G": self.optimizer_G.state_dict(), "optimizer_D": self.optimizer_D.state_dict()}
-
-    def load_optimizer_states(self, states):
-        if self.optimizer_G is None or self.optimizer_D is None:
-            raise ValueError("Optimizers have not been configured yet.")
-        for name in ("optimizer_G", "optimizer_D"):
-            if name not in states:
-                raise KeyError(f"{name} state not found in states")
-        self.optimizer_G.load_state_dict(states["optimizer_G"])
-        self.optimizer_D.load_state_dict(states["optimizer_D"])
+        return self._gan_optimizers(lr, betas, clip_grad_norm, ema_decay, pool_size, pool_seed)
 
     def configure_loss(self, **kwargs):
         self.loss_cycle = CycleConsistencyLoss()
@@ -795,15 +915,17 @@ class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
         self.loss_gan_disc = GANLossDiscriminator()
         if self.paired:
             self.loss_identity = IdentityLoss()
-        self.loss_kl = KLDivergenceLoss()
+        if self._variational:
+            self.loss_kl = KLDivergenceLoss()
+            self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
         self.lambda_gan = kwargs.get("lambda_gan", 1.0)
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
-        self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
         self.lambda_ssim, self.loss_ssim = _structural(kwargs)
 
     def _check_configured(self, need_opt=True):
-        if self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None or self.loss_kl is None:
+        if (self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None
+                or (self._variational and self.loss_kl is None)):
             raise ValueError("Loss functions have not been configured yet.")
         if self.paired and self.loss_identity is None:
             raise ValueError("Identity loss not configured for paired mode.")
@@ -812,57 +934,32 @@ class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
 
     def _skip_vae(self, ref_shape_src, vae):
         """Advance the eps stream past a VAE forward that is not computed."""
-        n, _, h, w = ref_shape_src.shape
-        lat = vae.variational_encoder_block.latent_dim
-        ops.next_eps((n, lat, h // 16, w // 16), ref_shape_src.device, skip=True)
+        ops.next_eps(_eps_shape(vae, ref_shape_src), ref_shape_src.device, skip=True)
 
-    def _forward_two_streams(self, x, y):
-        """The unpaired forward with the two translation directions on two streams (ops.DirectionFork): x -> G -> F -> DY on the
-        caller's stream, y -> F -> G -> DX on the second one, issued interleaved so that both have work from the start.  Same
-        results bit for bit: the eps draws are reserved in the reference's call order (G(x), [G(y)], F(G(x)), F(y), [F(x)],
-        G(F(y))), each discriminator still sees its two inputs in the reference's order (spectral norm's power iteration
-        advances per call: DY: G(x) then y; DX: F(y) then x)."""
-        n, _, h, w = x.shape
-        shp = (n, self.G.variational_encoder_block.latent_dim, h // 16, w // 16)
-        tk = ops.eps_tickets([(shp, False), (shp, True), (shp, False), (shp, False), (shp, True), (shp, False)], x.device)
-        ops.premeasure(x)
-        ops.premeasure(y)
-        fork = ops.DirectionFork(x.device)
-        (Gx, mu_x, lv_x), (Fy, mu_y, lv_y) = _vae_pair(self.G, x, tk[0], self.F, y, tk[3], fork)
-        (FGx, mu_FGx, lv_FGx), (GFy, mu_GFy, lv_GFy) = _vae_pair(self.F, Gx, tk[2], self.G, Fy, tk[5], fork)
-        DYGx = self.DY(Gx)                       # alternately again (32.64 -> 32.42 ms over three A/B pairs)
-        with fork.second():
-            DXFy = self.DX(Fy)
-        DYy = self.DY(y)
-        with fork.second():
-            DXx = self.DX(x)
-        fork.join()
-        return (Gx, mu_x, lv_x, FGx, mu_FGx, lv_FGx, Fy, mu_y, lv_y, GFy, mu_GFy, lv_GFy, DYGx, DXFy, DXx, DYy)
+    def _identity_pass(self, vae, image):
+        """G(y) / F(x) at their place in the reference's call order: they feed only the identity loss, so unpaired they are not
+        computed and only their eps draw is consumed."""
+        if self.paired:
+            return vae(image)[0]
+        self._skip_vae(image, vae)
 
     def _generator_losses(self, x, y, two_streams=False):
-        """Forward of both generators and everything G_loss needs (reference :1997-2018).  `two_streams`: see
-        `_forward_two_streams` (training_step / validation_step ask for it when the weight gradients overlap too)."""
-        Gy = Fx = None
+        """Forward of both generators and everything G_loss needs (reference :1997-2018, CycleAEGAN :1733-1753).  `two_streams`
+        (training_step asks for it when the weight gradients overlap too): the unpaired forward with x -> G -> F -> DY on the
+        caller's stream and y -> F -> G -> DX on a second one (_two_directions); the eps draws are reserved in the reference's
+        call order G(x), [G(y)], F(G(x)), F(y), [F(x)], G(F(y))."""
+        fork = tickets = None
         if two_streams and not self.paired and x.is_cuda:
-            (Gx, mu_x, lv_x, FGx, mu_FGx, lv_FGx, Fy, mu_y, lv_y, GFy, mu_GFy, lv_GFy, DYGx, DXFy, DXx,
-             DYy) = self._forward_two_streams(x, y)
-        else:
-            Gx, mu_x, lv_x = self.G(x)
-            if self.paired:
-                Gy, _, _ = self.G(y)
-            else:
-                self._skip_vae(y, self.G)
-            FGx, mu_FGx, lv_FGx = self.F(Gx)
-            Fy, mu_y, lv_y = self.F(y)
-            if self.paired:
-                Fx, _, _ = self.F(x)
-            else:
-                self._skip_vae(x, self.F)
-            GFy, mu_GFy, lv_GFy = self.G(Fy)
-            DYGx = self.DY(Gx)
-            DXFy = self.DX(Fy)
-            DXx = self.DX(x)
-            DYy = self.DY(y)
+            if self._variational:
+                shp = _eps_shape(self.G, x)
+                tk = ops.eps_tickets([(shp, False), (shp, True), (shp, False), (shp, False), (shp, True), (shp, False)], x.device)
+                tickets = (tk[0], tk[2], tk[3], tk[5])
+            fork = _fork(x, y)
+        (Gx, FGx, Fy, GFy), stats, Gy, Fx = _two_directions(self.G, self.F, x, y, fork, tickets,
+                                                             self._identity_pass if self._variational else None)
+        DYGx, DXFy, DXx, DYy = _discriminate(self.DY, self.DX, Gx, Fy, x, y, fork)
+        if fork is not None:
+            fork.join()
 
         t = {}
         t["loss_cycle"] = self.loss_cycle(x, y, FGx, GFy)
@@ -870,12 +967,15 @@ class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
         t["loss_gan_g_y_fake"], t["d_y_fake_mean"] = ops.mse_const(DYGx, 1.0)
         t["loss_gan_g_x_real"], t["d_x_real_mean"] = ops.mse_const(DXx, 0.0)
         t["loss_gan_g_y_real"], t["d_y_real_mean"] = ops.mse_const(DYy, 0.0)
-        t["loss_gan_g"] = ops.weighted_sum([t["loss_gan_g_x_fake"], t["loss_gan_g_y_fake"]], [1.0, 1.0])
-        t["loss_kl"] = ops.weighted_sum([self.loss_kl(mu_x, lv_x), self.loss_kl(mu_FGx, lv_FGx),
-                                         self.loss_kl(mu_y, lv_y), self.loss_kl(mu_GFy, lv_GFy)], [1.0] * 4)
-        terms = [t["loss_cycle"], t["loss_gan_g"], t["loss_kl"]]
-        weights = [self.lambda_cycle, self.lambda_gan, self.lambda_kl]
+        t["loss_gan_g"] = ops.weighted_sum([t[k] for k in self._GAN_G_TERMS], [1.0] * len(self._GAN_G_TERMS))
+        terms, weights = [t["loss_cycle"], t["loss_gan_g"]], [self.lambda_cycle, self.lambda_gan]
+        if self._variational:
+            t["loss_kl"] = ops.weighted_sum([self.loss_kl(stats[2 * i], stats[2 * i + 1]) for i in range(4)], [1.0] * 4)
+            terms.append(t["loss_kl"])
+            weights.append(self.lambda_kl)
         if self.paired:
+            if not self._variational:            # CycleAEGAN's identity passes follow the discriminators (reference :1749-1751)
+                Fx, Gy = self.F(x), self.G(y)
             t["loss_identity"] = self.loss_identity(x, y, Fx, Gy)
             terms.append(t["loss_identity"])
             weights.append(self.lambda_identity)
@@ -898,20 +998,13 @@ class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
                     "loss_gan_g_y_fake", "loss_kl")
     _MEAN_KEYS = ("d_x_real_mean", "d_x_fake_mean", "d_y_real_mean", "d_y_fake_mean")
 
-    def _metrics(self, t, with_means):
-        keys = list(self._METRIC_KEYS) + (list(self._MEAN_KEYS) if with_means else [])
+    def _report_spec(self, training):
+        keys = self._METRIC_KEYS + (self._MEAN_KEYS if training else ())
         if self.paired:
-            keys.append("loss_identity")
+            keys += ("loss_identity",)
         if self.loss_ssim is not None:
-            keys.append("loss_ssim")
-        if with_means:                                  # the training step: what the two optimizer steps left on the device
-            clip = _clip_scalars(_G=self.optimizer_G, _D=self.optimizer_D)
-            t = dict(t, **clip)
-            keys += list(clip)
-        host = _metrics_to_host({k: t[k] for k in keys}, self.grad_reducer if with_means else None)
-        out = {"total_loss": host["G_loss"] + host["D_loss"]}
-        out.update(host)
-        return out
+            keys += ("loss_ssim",)
+        return (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + (() if training else _GX_FY)
 
     def _pooled_d_terms(self, t, Gx, Fy):
         """The discriminators' fake terms with image history pools (_PoolMixin), after the forward (both direction streams are
@@ -934,49 +1027,19 @@ class CycleVAEGAN(_PoolMixin, _EmaMixin, nn.Module):
         _refuse_training_in_ema_scope(self)
         self._check_configured()
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
-        g_params = self.optimizer_G.params
-        d_params = self.optimizer_D.params
-
-        red = self.grad_reducer
         self.optimizer_G.zero_grad()
         t, Gx, Fy = self._generator_losses(x, y, two_streams=ops.two_directions())
         if self.image_pools:
             self._pooled_d_terms(t, Gx, Fy)
-        if red is not None:
-            red.begin(self.optimizer_G)          # F+G buckets are all-reduced from inside the backward as they complete
-        # generator gradients reach F and G only (the discriminators contribute their data gradient)
-        with ops.no_wgrad(d_params):
-            ops.backward_overlapped(t["G_loss"], inputs=g_params, retain_graph=True)
-        if red is not None:
-            red.start(self.optimizer_G)          # whatever is left; it runs under the D backward below
-        # discriminator gradients from the same activations reach DX and DY only — what detaching
-        # G(x), F(y) achieves in the reference (:2028-2029).  Neither this backward nor D_loss reads a
-        # generator parameter, so running it before optimizer_G.step() changes nothing.
-        self.optimizer_D.zero_grad()
-        if red is not None:
-            red.begin(self.optimizer_D)
-        with ops.no_dgrad([self.DX.model[0]._spec, self.DY.model[0]._spec]):
-            ops.backward_overlapped(t["D_loss"], inputs=d_params)
-        if red is not None:
-            red.start(self.optimizer_D)
-            red.finish(self.optimizer_G)
-        self.optimizer_G.step()
-        if red is not None:
-            red.finish(self.optimizer_D)
-        self.optimizer_D.step()
-        return self._metrics(t, with_means=True)
+        self._alternating_step(t["G_loss"], t["D_loss"])
+        return _report(self, t, self._report_spec(True), True)
 
     def validation_step(self, batch):
         self._check_configured(need_opt=False)
         with torch.no_grad():
-            paired = self.paired
             x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
             t, Gx, Fy = self._generator_losses(x, y)
-            m = self._metrics(t, with_means=False)
-            m["Gx"] = Gx.detach()
-            m["Fy"] = Fy.detach()
-            assert paired == self.paired
-            return m
+            return _report(self, t, self._report_spec(False), False, Gx=Gx.detach(), Fy=Fy.detach())
 
 
 class CycleAEGAN(CycleVAEGAN):
@@ -986,26 +1049,15 @@ class CycleAEGAN(CycleVAEGAN):
     (`loss_gan_g = loss_gan_g_x + loss_gan_g_y`, real + fake terms, :1745-1748) where CycleVAEGAN takes only the fake
     terms — the real terms have no gradient into F and G, but they are part of `G_loss` and of the `loss_gan_g` metric.
     The step itself (one discriminator pass serving both phases, exchange hooks, side stream) is CycleVAEGAN's."""
+    _variational = False
+    _GAN_G_TERMS = ("loss_gan_g_x_real", "loss_gan_g_x_fake", "loss_gan_g_y_real", "loss_gan_g_y_fake")
+    _METRIC_KEYS = tuple(k for k in CycleVAEGAN._METRIC_KEYS if k != "loss_kl")
 
     def __init__(self, paired=True):
-        nn.Module.__init__(self)
-        self.F = Autoencoder()
-        self.G = Autoencoder()
-        self.DX = Discriminator()
-        self.DY = Discriminator()
-        self.paired = paired
-        self.apply(self._init_weights)
-        self.debug_mode = False
-        self.debug_info = {}
-        self.optimizer_G = None
-        self.optimizer_D = None
-        self.loss_cycle = None
-        self.loss_gan_gen = None
-        self.loss_gan_disc = None
-        self.loss_identity = None
-        self.loss_ssim = None
-        self.lambda_ssim = 0.0
-        self.grad_reducer = None
+        super().__init__(paired=paired)
+
+    def _make_generator(self, latent_dim):
+        return Autoencoder()
 
     def forward(self, x, y):
         x, y = ops.to_nhwc(x), ops.to_nhwc(y)
@@ -1016,78 +1068,6 @@ class CycleAEGAN(CycleVAEGAN):
         Fx = self.F(x)
         GFy = self.G(Fy)
         return Gx, FGx, Fy, GFy, self.DY(Gx), self.DX(Fy), self.DX(x), self.DY(y), Gy, Fx
-
-    def configure_loss(self, **kwargs):
-        self.loss_cycle = CycleConsistencyLoss()
-        self.loss_gan_gen = GANLossGenerator()
-        self.loss_gan_disc = GANLossDiscriminator()
-        if self.paired:
-            self.loss_identity = IdentityLoss()
-        self.lambda_gan = kwargs.get("lambda_gan", 1.0)
-        self.lambda_identity = kwargs.get("lambda_identity", 5.0)
-        self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
-        self.lambda_ssim, self.loss_ssim = _structural(kwargs)
-
-    def _check_configured(self, need_opt=True):
-        if self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None:
-            raise ValueError("Loss functions have not been configured yet.")
-        if self.paired and self.loss_identity is None:
-            raise ValueError("Identity loss not configured for paired mode.")
-        if need_opt and (self.optimizer_G is None or self.optimizer_D is None):
-            raise ValueError("Optimizers have not been configured yet.")
-
-    def _generator_losses(self, x, y, two_streams=False):
-        """reference :1733-1753; G(y), F(x) feed only the identity loss and are skipped when unpaired.  `two_streams`: the two
-        translation directions on two streams (CycleVAEGAN._forward_two_streams; no eps here)."""
-        if two_streams and not self.paired and x.is_cuda:
-            ops.premeasure(x)
-            ops.premeasure(y)
-            fork = ops.DirectionFork(x.device)
-            Gx, Fy = _ae_pair(self.G, x, self.F, y, fork)
-            FGx, GFy = _ae_pair(self.F, Gx, self.G, Fy, fork)
-            DYGx = self.DY(Gx)
-            with fork.second():
-                DXFy = self.DX(Fy)
-            DYy = self.DY(y)
-            with fork.second():
-                DXx = self.DX(x)
-            fork.join()
-        else:
-            Gx = self.G(x)
-            FGx = self.F(Gx)
-            Fy = self.F(y)
-            GFy = self.G(Fy)
-            DYGx = self.DY(Gx)
-            DXFy = self.DX(Fy)
-            DXx = self.DX(x)
-            DYy = self.DY(y)
-        t = {}
-        t["loss_cycle"] = self.loss_cycle(x, y, FGx, GFy)
-        t["loss_gan_g_x_fake"], t["d_x_fake_mean"] = ops.mse_const(DXFy, 1.0)
-        t["loss_gan_g_y_fake"], t["d_y_fake_mean"] = ops.mse_const(DYGx, 1.0)
-        t["loss_gan_g_x_real"], t["d_x_real_mean"] = ops.mse_const(DXx, 0.0)
-        t["loss_gan_g_y_real"], t["d_y_real_mean"] = ops.mse_const(DYy, 0.0)
-        t["loss_gan_g"] = ops.weighted_sum([t["loss_gan_g_x_real"], t["loss_gan_g_x_fake"], t["loss_gan_g_y_real"],
-                                            t["loss_gan_g_y_fake"]], [1.0] * 4)
-        terms, weights = [t["loss_cycle"], t["loss_gan_g"]], [self.lambda_cycle, self.lambda_gan]
-        if self.paired:
-            t["loss_identity"] = self.loss_identity(x, y, self.F(x), self.G(y))
-            terms.append(t["loss_identity"])
-            weights.append(self.lambda_identity)
-        if self.loss_ssim is not None:               # the structural cycle term; FGx and GFy are joined by now, as for loss_cycle
-            t["loss_ssim"] = ops.weighted_sum([self.loss_ssim(FGx, x), self.loss_ssim(GFy, y)], [1.0, 1.0])
-            terms.append(t["loss_ssim"])
-            weights.append(self.lambda_ssim)
-        t["G_loss"] = ops.weighted_sum(terms, weights)
-        t["D_loss_x_real"], _ = ops.mse_const(DXx, 1.0)
-        t["D_loss_x_fake"], _ = ops.mse_const(DXFy, 0.0)
-        t["D_loss_y_real"], _ = ops.mse_const(DYy, 1.0)
-        t["D_loss_y_fake"], _ = ops.mse_const(DYGx, 0.0)
-        t["D_loss"] = ops.weighted_sum([t["D_loss_x_real"], t["D_loss_x_fake"], t["D_loss_y_real"], t["D_loss_y_fake"]],
-                                       [1.0] * 4)
-        return t, Gx, Fy
-
-    _METRIC_KEYS = tuple(k for k in CycleVAEGAN._METRIC_KEYS if k != "loss_kl")
 
 
 class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
@@ -1104,11 +1084,25 @@ class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
         self.lambda_cycle = 0
         self.lambda_kl = 0
 
+    def forward(self, x, y):
+        return self._fwd(x, y, False)
+
+    def _fwd(self, x, y, two_streams):
+        """-> Gx, FGx, Fy, GFy, then for VAEs mu_x, logvar_x, mu_FGx, logvar_FGx, mu_y, logvar_y, mu_GFy, logvar_GFy; eps is drawn
+        in the order G(x), F(G(x)), F(y), G(F(y)) (:1489-1494) — on two streams (_two_directions) from tickets reserved so."""
+        x, y = ops.to_nhwc(x), ops.to_nhwc(y)
+        fork = tickets = None
+        if two_streams and x.is_cuda:
+            if self._variational:
+                tickets = ops.eps_tickets([(_eps_shape(self.G, x), False)] * 4, x.device)
+            fork = _fork(x, y)
+        images, stats, _, _ = _two_directions(self.G, self.F, x, y, fork, tickets)
+        if fork is not None:
+            fork.join()
+        return images + stats
+
     def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
-        _refuse_pool(self, pool_size)
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
-                                   ema_decay=_ema_decay(ema_decay))
-        return self.optimizer
+        return self._single_optimizer(self.parameters(), lr, betas, clip_grad_norm, ema_decay, pool_size)
 
     def _check_configured(self, need_opt=True):
         if self.loss_cycle is None or (self._variational and self.loss_kl is None):
@@ -1135,37 +1129,23 @@ class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
         t["G_loss"] = ops.weighted_sum(terms, weights)
         return t, Gx, Fy
 
+    def _report_spec(self, training):
+        """the reference's key order (:1421-1433, :1547-1561): total_loss, loss_cycle, [loss_kl], G_loss, [Gx, Fy], [loss_trans]"""
+        return ((("total_loss", "G_loss"),) + _same("loss_cycle", *(("loss_kl",) if self._variational else ()), "G_loss")
+                + (() if training else _GX_FY) + (_same("loss_trans") if self.paired else ()))
+
     def training_step(self, batch):
         _refuse_training_in_ema_scope(self)
         self._check_configured()
         t, _, _ = self._losses(batch)
         _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
-        clip = _clip_scalars(**{"": self.optimizer})
-        host = _metrics_to_host(dict(t, **clip), self.grad_reducer)
-        m = self._ordered(host)
-        if self.paired:
-            m["loss_trans"] = host["loss_trans"]
-        m.update({k: host[k] for k in clip})
-        return m
-
-    def _ordered(self, host):
-        """the reference's key order (:1421-1433, :1547-1561): total_loss, loss_cycle, [loss_kl], G_loss, [loss_trans]"""
-        m = {"total_loss": host["G_loss"], "loss_cycle": host["loss_cycle"]}
-        if self._variational:
-            m["loss_kl"] = host["loss_kl"]
-        m["G_loss"] = host["G_loss"]
-        return m
+        return _report(self, t, self._report_spec(True), True)
 
     def validation_step(self, batch):
         self._check_configured(need_opt=False)
         with torch.no_grad():
             t, Gx, Fy = self._losses(batch)
-            host = _metrics_to_host(t)
-            m = self._ordered(host)
-            m["Gx"], m["Fy"] = Gx.detach(), Fy.detach()
-            if self.paired:
-                m["loss_trans"] = host["loss_trans"]
-            return m
+            return _report(self, t, self._report_spec(False), False, Gx=Gx.detach(), Fy=Fy.detach())
 
 
 class CycleAE(_CycleNoGAN):
@@ -1177,24 +1157,6 @@ class CycleAE(_CycleNoGAN):
         self.F = Autoencoder()
         self.G = Autoencoder()
         self._init_common(paired)
-
-    def forward(self, x, y):
-        return self._fwd(x, y, False)
-
-    def _fwd(self, x, y, two_streams):
-        x, y = ops.to_nhwc(x), ops.to_nhwc(y)
-        if two_streams and x.is_cuda:            # the two translation directions on two streams (CycleVAEGAN._forward_two_streams)
-            ops.premeasure(x)
-            ops.premeasure(y)
-            fork = ops.DirectionFork(x.device)
-            Gx, Fy = _ae_pair(self.G, x, self.F, y, fork)
-            FGx, GFy = _ae_pair(self.F, Gx, self.G, Fy, fork)
-            fork.join()
-            return Gx, FGx, Fy, GFy
-        Gx = self.G(x)
-        FGx = self.F(Gx)
-        Fy = self.F(y)
-        return Gx, FGx, Fy, self.G(Fy)
 
     def configure_loss(self, **kwargs):
         self.loss_cycle = CycleConsistencyLoss()
@@ -1214,28 +1176,6 @@ class CycleVAE(_CycleNoGAN):
         self.G = VariationalAutoencoder(latent_dim)
         self._init_common(paired)
 
-    def forward(self, x, y):
-        return self._fwd(x, y, False)
-
-    def _fwd(self, x, y, two_streams):
-        x, y = ops.to_nhwc(x), ops.to_nhwc(y)
-        if two_streams and x.is_cuda:            # as CycleVAEGAN._forward_two_streams; eps reserved in the order G(x), F(G(x)), F(y), G(F(y))
-            n, _, h, w = x.shape
-            shp = (n, self.G.variational_encoder_block.latent_dim, h // 16, w // 16)
-            tk = ops.eps_tickets([(shp, False)] * 4, x.device)
-            ops.premeasure(x)
-            ops.premeasure(y)
-            fork = ops.DirectionFork(x.device)
-            (Gx, mu_x, logvar_x), (Fy, mu_y, logvar_y) = _vae_pair(self.G, x, tk[0], self.F, y, tk[2], fork)
-            (FGx, mu_FGx, logvar_FGx), (GFy, mu_GFy, logvar_GFy) = _vae_pair(self.F, Gx, tk[1], self.G, Fy, tk[3], fork)
-            fork.join()
-            return Gx, FGx, Fy, GFy, mu_x, logvar_x, mu_FGx, logvar_FGx, mu_y, logvar_y, mu_GFy, logvar_GFy
-        Gx, mu_x, logvar_x = self.G(x)
-        FGx, mu_FGx, logvar_FGx = self.F(Gx)
-        Fy, mu_y, logvar_y = self.F(y)
-        GFy, mu_GFy, logvar_GFy = self.G(Fy)
-        return Gx, FGx, Fy, GFy, mu_x, logvar_x, mu_FGx, logvar_FGx, mu_y, logvar_y, mu_GFy, logvar_GFy
-
     def configure_loss(self, **kwargs):
         self.loss_cycle = CycleConsistencyLoss()
         if self.paired:
@@ -1245,10 +1185,36 @@ class CycleVAE(_CycleNoGAN):
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
 
 
-class DoubleAutoencoder(_OptimizerStatesMixin, nn.Module):
+class _DoubleStep(_OptimizerStatesMixin, nn.Module):
+    """The step of the two pretraining models: one shared encoder, a decoder per modality, one Adam over everything."""
+
+    def forward(self, x, y):
+        return self._fwd(x, y, False)
+
+    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
+        return self._single_optimizer(self.parameters(), lr, betas, clip_grad_norm, ema_decay, pool_size)
+
+    def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
+        self._check_configured()
+        t, _, _ = self._losses(batch)
+        _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
+        return _report(self, t, self._TRAIN, True)
+
+    def validation_step(self, batch):
+        """Gx / Fy are the translations: the encoder runs four times, and a VAE draws eps for each."""
+        self._check_configured(need_opt=False)
+        with torch.no_grad():
+            t, x, y = self._losses(batch)
+            return _report(self, t, self._VALIDATION, False, Gx=self.translate_A_to_B(x), Fy=self.translate_B_to_A(y))
+
+
+class DoubleAutoencoder(_DoubleStep):
     """One shared encoder, decoder_A reconstructs the source and decoder_B the target modality — the pretraining model
     for CycleAE (reference Networks.py:415-606).  The encoder runs twice per step, so its weight gradients accumulate
     from both uses (the backward kernels add into the flat gradient buffer)."""
+    _TRAIN = _same("G_loss", "loss_recon_A", "loss_recon_B") + (("total_loss", "G_loss"),)
+    _VALIDATION = (("G_loss", "G_loss"), ("total_loss", "G_loss")) + _same("loss_recon_A", "loss_recon_B") + _GX_FY
 
     def __init__(self):
         super().__init__()
@@ -1259,15 +1225,10 @@ class DoubleAutoencoder(_OptimizerStatesMixin, nn.Module):
         self.grad_reducer = None
         self.loss_fn = None
 
-    def forward(self, x, y):
-        return self._fwd(x, y, False)
-
     def _fwd(self, x, y, two_streams):
         x, y = ops.to_nhwc(x), ops.to_nhwc(y)
-        if two_streams and x.is_cuda:            # the two modalities on two streams (ops.DirectionFork; the shared encoder's
-            ops.premeasure(x)                    # gradients meet on the one weight-gradient stream)
-            ops.premeasure(y)
-            fork = ops.DirectionFork(x.device)
+        if two_streams and x.is_cuda:            # the two modalities on two streams (the shared encoder's gradients meet on the
+            fork = _fork(x, y)                   # one weight-gradient stream)
             a = self.decoder_A(self.encoder(x))
             with fork.second():
                 b = self.decoder_B(self.encoder(y))
@@ -1290,14 +1251,14 @@ class DoubleAutoencoder(_OptimizerStatesMixin, nn.Module):
         cycle_ae.F.decoder.load_state_dict(self.decoder_A.state_dict())
         return cycle_ae
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
-        _refuse_pool(self, pool_size)
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
-                                   ema_decay=_ema_decay(ema_decay))
-        return self.optimizer
-
     def configure_loss(self, **kwargs):
         self.loss_fn = TranslationLoss()
+
+    def _check_configured(self, need_opt=True):
+        if self.loss_fn is None:
+            raise ValueError("Loss function has not been configured yet.")
+        if need_opt and self.optimizer is None:
+            raise ValueError("Optimizer has not been configured yet.")
 
     def _losses(self, batch):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
@@ -1306,34 +1267,14 @@ class DoubleAutoencoder(_OptimizerStatesMixin, nn.Module):
         t["G_loss"] = ops.weighted_sum([t["loss_recon_A"], t["loss_recon_B"]], [1.0, 1.0])
         return t, x, y
 
-    def training_step(self, batch):
-        _refuse_training_in_ema_scope(self)
-        if self.loss_fn is None:
-            raise ValueError("Loss function has not been configured yet.")
-        if self.optimizer is None:
-            raise ValueError("Optimizer has not been configured yet.")
-        t, _, _ = self._losses(batch)
-        _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
-        clip = _clip_scalars(**{"": self.optimizer})
-        h = _metrics_to_host(dict(t, **clip), self.grad_reducer)
-        m = {"G_loss": h["G_loss"], "loss_recon_A": h["loss_recon_A"], "loss_recon_B": h["loss_recon_B"], "total_loss": h["G_loss"]}
-        m.update({k: h[k] for k in clip})
-        return m
 
-    def validation_step(self, batch):
-        if self.loss_fn is None:
-            raise ValueError("Loss function has not been configured yet.")
-        with torch.no_grad():
-            t, x, y = self._losses(batch)
-            h = _metrics_to_host(t)
-            return {"G_loss": h["G_loss"], "total_loss": h["G_loss"], "loss_recon_A": h["loss_recon_A"],
-                    "loss_recon_B": h["loss_recon_B"], "Gx": self.translate_A_to_B(x), "Fy": self.translate_B_to_A(y)}
-
-
-class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
+class DoubleVariationalAutoencoder(_DoubleStep):
     """Shared encoder, one VAE bottleneck and one decoder per modality — the pretraining model for CycleVAE / CycleVAEGAN
     (reference Networks.py:608-852).  eps draws per forward: block A on enc(x), then block B on enc(y); validation adds one
     per translation."""
+    _TRAIN = _same("G_loss", "loss_recon_A", "loss_recon_B", "loss_kl", "loss_kl_A", "loss_kl_B") + (("total_loss", "G_loss"),)
+    _VALIDATION = ((("G_loss", "G_loss"), ("total_loss", "G_loss"))
+                   + _same("loss_recon_A", "loss_recon_B", "loss_kl", "loss_kl_A", "loss_kl_B") + _GX_FY)
 
     def __init__(self, latent_dim=64):
         super().__init__()
@@ -1354,18 +1295,13 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
     def _init_weights(self, module):
         _kaiming_relu_init(module)
 
-    def forward(self, x, y):
-        return self._fwd(x, y, False)
-
     def _fwd(self, x, y, two_streams):
         x, y = ops.to_nhwc(x), ops.to_nhwc(y)
         if two_streams and x.is_cuda:            # the two modalities on two streams; eps: block A's draw, then block B's
             n, _, h, w = x.shape
             shp = (n, self.vae_encoder_block_A.latent_dim, h // 16, w // 16)
             tk = ops.eps_tickets([(shp, False)] * 2, x.device)
-            ops.premeasure(x)
-            ops.premeasure(y)
-            fork = ops.DirectionFork(x.device)
+            fork = _fork(x, y)
             with ops.use_ticket(tk[0]):
                 z_x, mu_x, logvar_x = self.vae_encoder_block_A(self.encoder(x))
             Gx = self.decoder_A(self.vae_decoder_block_A(z_x))
@@ -1401,16 +1337,16 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             gen.decoder.load_state_dict(getattr(self, "decoder_" + sfx).state_dict())
         return cycle_vae
 
-    def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
-        _refuse_pool(self, pool_size)
-        self.optimizer = FusedAdam(self.parameters(), lr=lr, betas=betas, max_grad_norm=_max_grad_norm(clip_grad_norm),
-                                   ema_decay=_ema_decay(ema_decay))
-        return self.optimizer
-
     def configure_loss(self, **kwargs):
         self.loss_trans_fn = TranslationLoss()
         self.loss_kl_fn = KLDivergenceLoss()
         self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
+
+    def _check_configured(self, need_opt=True):
+        if self.loss_trans_fn is None or self.loss_kl_fn is None:
+            raise ValueError("Loss functions have not been configured yet.")
+        if need_opt and self.optimizer is None:
+            raise ValueError("Optimizer has not been configured yet.")
 
     def _losses(self, batch):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
@@ -1421,59 +1357,17 @@ class DoubleVariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         t["G_loss"] = ops.weighted_sum([t["loss_recon_A"], t["loss_recon_B"], t["loss_kl"]], [1.0, 1.0, self.lambda_kl])
         return t, x, y
 
-    def training_step(self, batch):
-        _refuse_training_in_ema_scope(self)
-        if self.loss_trans_fn is None or self.loss_kl_fn is None:
-            raise ValueError("Loss functions have not been configured yet.")
-        if self.optimizer is None:
-            raise ValueError("Optimizer has not been configured yet.")
-        t, _, _ = self._losses(batch)
-        _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
-        clip = _clip_scalars(**{"": self.optimizer})
-        h = _metrics_to_host(dict(t, **clip), self.grad_reducer)
-        m = {"G_loss": h["G_loss"], "loss_recon_A": h["loss_recon_A"], "loss_recon_B": h["loss_recon_B"], "loss_kl": h["loss_kl"],
-             "loss_kl_A": h["loss_kl_A"], "loss_kl_B": h["loss_kl_B"], "total_loss": h["G_loss"]}
-        m.update({k: h[k] for k in clip})
-        return m
 
-    def validation_step(self, batch):
-        if self.loss_trans_fn is None or self.loss_kl_fn is None:
-            raise ValueError("Loss functions have not been configured yet.")
-        with torch.no_grad():
-            t, x, y = self._losses(batch)
-            h = _metrics_to_host(t)
-            return {"G_loss": h["G_loss"], "total_loss": h["G_loss"], "loss_recon_A": h["loss_recon_A"],
-                    "loss_recon_B": h["loss_recon_B"], "loss_kl": h["loss_kl"], "loss_kl_A": h["loss_kl_A"],
-                    "loss_kl_B": h["loss_kl_B"], "Gx": self.translate_A_to_B(x), "Fy": self.translate_B_to_A(y)}
-
-
-class _SingleGAN(_PoolMixin, _EmaMixin, nn.Module):
+class _SingleGAN(_GanMixin, nn.Module):
     """One generator G: X->Y and one discriminator D on Y, alternating G / D updates — the shared step of AEGAN and VAEGAN
     (reference Networks.py:991-1348).  As in CycleVAEGAN the discriminator runs once per step: the G phase takes its data
     gradient, the D phase its weight gradients from the same activations.  VAEGAN is written that way in the reference
     (`DGx.detach()`, `retain_graph`, :1277-1287); AEGAN re-runs D on the detached G(x) after the generator update
     (:1105-1108), which reproduces the same outputs because that update does not touch D."""
+    _generators, _discriminators = ("G",), ("D",)
 
     def configure_optimizers(self, lr=2e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0, pool_seed=0):
-        self._make_pools(("D",), pool_size, pool_seed)    # pool_size > 0: D's image history pool of G(x) (_PoolMixin)
-        bound = _max_grad_norm(clip_grad_norm)            # one bound, two norms (CycleVAEGAN.configure_optimizers)
-        self.optimizer_G = FusedAdam(self.G.parameters(), lr=lr, betas=betas, max_grad_norm=bound, ema_decay=_ema_decay(ema_decay))
-        self.optimizer_D = FusedAdam(self.D.parameters(), lr=lr, betas=betas, max_grad_norm=bound)
-        return self.optimizer_G, self.optimizer_D
-
-    def save_optimizer_states(self):
-        if self.optimizer_G is None or self.optimizer_D is None:
-            raise ValueError("Optimizers have not been configured yet.")
-        return {"optimizer_G": self.optimizer_G.state_dict(), "optimizer_D": self.optimizer_D.state_dict()}
-
-    def load_optimizer_states(self, states):
-        if self.optimizer_G is None or self.optimizer_D is None:
-            raise ValueError("Optimizers have not been configured yet.")
-        for name in ("optimizer_G", "optimizer_D"):
-            if name not in states:
-                raise KeyError(f"{name} state not found in states")
-        self.optimizer_G.load_state_dict(states["optimizer_G"])
-        self.optimizer_D.load_state_dict(states["optimizer_D"])
+        return self._gan_optimizers(lr, betas, clip_grad_norm, ema_decay, pool_size, pool_seed)
 
     def _gan_terms(self, t, DGx, Dy):
         """LSGAN terms on one discriminator pass: generator (real -> 0, fake -> 1, Losses.py:67-83) and discriminator
@@ -1496,33 +1390,30 @@ class _SingleGAN(_PoolMixin, _EmaMixin, nn.Module):
         if self.debug_mode:
             self._debug_store().update(fake=fake, d_fake=shown)
 
-    def _alternating_step(self, t):
-        g_params, d_params = self.optimizer_G.params, self.optimizer_D.params
-        red = self.grad_reducer
+    def training_step(self, batch):
+        _refuse_training_in_ema_scope(self)
+        self._check_configured()
         self.optimizer_G.zero_grad()
-        if red is not None:
-            red.begin(self.optimizer_G)
-        with ops.no_wgrad(d_params):
-            ops.backward_overlapped(t["G_loss"], inputs=g_params, retain_graph=True)
-        if red is not None:
-            red.start(self.optimizer_G)
-        self.optimizer_D.zero_grad()
-        if red is not None:
-            red.begin(self.optimizer_D)
-        with ops.no_dgrad([self.D.model[0]._spec]):
-            ops.backward_overlapped(t.get("D_loss_backward", t["D_loss"]), inputs=d_params)
-        if red is not None:
-            red.start(self.optimizer_D)
-            red.finish(self.optimizer_G)
-        self.optimizer_G.step()
-        if red is not None:
-            red.finish(self.optimizer_D)
-        self.optimizer_D.step()
+        t, Gx = self._losses(batch)
+        if self.image_pools:
+            self._pooled_d_terms(t, Gx)
+        self._alternating_step(t["G_loss"], t.get("D_loss_backward", t["D_loss"]))
+        return _report(self, t, self._TRAIN, True)
+
+    def validation_step(self, batch):
+        with torch.no_grad():
+            t, Gx = self._losses(batch)
+            return _report(self, t, self._VALIDATION, False, Gx=Gx)
 
 
 class AEGAN(_SingleGAN):
     """Autoencoder generator + discriminator: L1(G(x), y) + lambda_gan * LSGAN + lambda_identity * L1(G(y), y)
     (reference Networks.py:991-1188)."""
+    _TRAIN = (_same("G_loss", "D_loss", "D_loss_real", "D_loss_fake", "loss_trans") + (("loss_gan_g", "gan_g"),)
+              + _same("loss_identity", "d_y_mean", "d_gx_mean"))
+    _VALIDATION = ((("total_loss", ("G_loss", "D_loss")),) + _same("G_loss", "D_loss", "D_loss_real", "D_loss_fake", "loss_trans")
+                   + (("loss_gan_g", "gan_g"), ("loss_gan_g_real", "gan_g_real"), ("loss_gan_g_fake", "gan_g_fake"))
+                   + _same("loss_identity") + _GX)
 
     def __init__(self):
         super().__init__()
@@ -1576,35 +1467,19 @@ class AEGAN(_SingleGAN):
         t["G_loss"] = ops.weighted_sum([t["loss_trans"], t["gan_g"], t["loss_identity"]], [1.0, self.lambda_gan, self.lambda_identity])
         return t, Gx
 
-    def training_step(self, batch):
-        _refuse_training_in_ema_scope(self)
-        self._check_configured()
-        t, Gx = self._losses(batch)
-        if self.image_pools:
-            self._pooled_d_terms(t, Gx)
-        self._alternating_step(t)
-        clip = _clip_scalars(_G=self.optimizer_G, _D=self.optimizer_D)
-        h = _metrics_to_host(dict(t, **clip), self.grad_reducer)
-        m = {"G_loss": h["G_loss"], "D_loss": h["D_loss"], "D_loss_real": h["D_loss_real"], "D_loss_fake": h["D_loss_fake"],
-             "loss_trans": h["loss_trans"], "loss_gan_g": h["gan_g"], "loss_identity": h["loss_identity"],
-             "d_y_mean": h["d_y_mean"], "d_gx_mean": h["d_gx_mean"]}
-        m.update({k: h[k] for k in clip})
-        return m
-
     def validation_step(self, batch):
         self._check_configured()            # the reference's AEGAN wants its optimizers even to validate (:1145)
-        with torch.no_grad():
-            t, Gx = self._losses(batch)
-            h = _metrics_to_host(t)
-            return {"total_loss": h["G_loss"] + h["D_loss"], "G_loss": h["G_loss"], "D_loss": h["D_loss"],
-                    "D_loss_real": h["D_loss_real"], "D_loss_fake": h["D_loss_fake"], "loss_trans": h["loss_trans"],
-                    "loss_gan_g": h["gan_g"], "loss_gan_g_real": h["gan_g_real"], "loss_gan_g_fake": h["gan_g_fake"],
-                    "loss_identity": h["loss_identity"], "Gx": Gx}
+        return super().validation_step(batch)
 
 
 class VAEGAN(_SingleGAN):
     """VAE generator + discriminator: lambda_recon * L1(G(x), y) + lambda_gan * LSGAN + lambda_identity * L1(G(y), y) +
     lambda_kl * KL(mu_x, logvar_x)  (reference Networks.py:1190-1348; eps is drawn for G(x), then for G(y))."""
+    _TRAIN = (_same("G_loss", "D_loss") + (("loss_gan_disc_real", "D_loss_real"), ("loss_gan_disc_fake", "D_loss_fake"))
+              + _same("loss_trans") + (("loss_gan_real", "gan_g_real"), ("loss_gan_fake", "gan_g_fake"))
+              + _same("loss_identity", "loss_kl"))
+    _VALIDATION = ((("total_loss", ("G_loss", "D_loss")),) + _same("G_loss", "D_loss", "loss_trans")
+                   + (("loss_gan_real", "gan_g_real"), ("loss_gan_fake", "gan_g_fake")) + _same("loss_identity", "loss_kl") + _GX)
 
     def __init__(self, latent_dim=64):
         super().__init__()
@@ -1637,6 +1512,10 @@ class VAEGAN(_SingleGAN):
     def enable_debug_mode(self, enabled=True):
         self.debug_mode = enabled
 
+    def _check_configured(self):
+        if self.optimizer_G is None or self.optimizer_D is None:
+            raise ValueError("Optimizers have not been configured yet.")
+
     def _losses(self, batch):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         Gx, mu, logvar, Gy, _, _, DGx, Dy = self(x, y)
@@ -1652,28 +1531,7 @@ class VAEGAN(_SingleGAN):
         return t, Gx
 
     def training_step(self, batch):
-        _refuse_training_in_ema_scope(self)
-        if self.optimizer_G is None or self.optimizer_D is None:
-            raise ValueError("Optimizers have not been configured yet.")
-        t, Gx = self._losses(batch)
-        if self.image_pools:
-            self._pooled_d_terms(t, Gx)
-        self._alternating_step(t)
-        clip = _clip_scalars(_G=self.optimizer_G, _D=self.optimizer_D)
-        h = _metrics_to_host(dict(t, **clip), self.grad_reducer)
-        m = {"G_loss": h["G_loss"], "D_loss": h["D_loss"], "loss_gan_disc_real": h["D_loss_real"],
-             "loss_gan_disc_fake": h["D_loss_fake"], "loss_trans": h["loss_trans"], "loss_gan_real": h["gan_g_real"],
-             "loss_gan_fake": h["gan_g_fake"], "loss_identity": h["loss_identity"], "loss_kl": h["loss_kl"]}
-        m.update({k: h[k] for k in clip})
+        m = super().training_step(batch)
         if self.debug_mode:
             m["debug_info"] = self.debug_info
         return m
-
-    def validation_step(self, batch):
-        with torch.no_grad():
-            t, Gx = self._losses(batch)
-            h = _metrics_to_host(t)
-            return {"total_loss": h["G_loss"] + h["D_loss"], "G_loss": h["G_loss"], "D_loss": h["D_loss"],
-                    "loss_trans": h["loss_trans"], "loss_gan_real": h["gan_g_real"], "loss_gan_fake": h["gan_g_fake"],
-                    "loss_identity": h["loss_identity"], "loss_kl": h["loss_kl"], "Gx": Gx}
-
