@@ -406,6 +406,45 @@ int vcg_swap(float* a, float* b, size_t n, void* stream);
 int vcg_pool_exchange(const float* fake, float* pool, float* out, const int32_t* plan, int N, size_t elems, int capacity,
                       void* stream);
 
+/* The sampling translator (translate.py --samples K; new: the reference has no inference path) — csrc/sample_stats.hip -------- */
+/* Broadcast reparameterisation for inference (new: the reference has no inference path): forward only.  mu, lv: N physical latent
+   maps of `per` floats each (per a multiple of 4).  For the samples j = first .. first + k - 1 of the K of every map
+     z[(n, j)] = mu[n] + temperature * eps[(n, j)] * exp(0.5 * clamp(lv[n], -10, 10)),
+   z (and eps_out, if not NULL: the eps used) sample-major within a map for this chunk: (N, k, per).
+   eps == NULL: drawn on the device; sample (n, j) uses the values vcg_randn writes for (seed, offset + (n K + j) per / 4), per
+   values long — a draw depends on (seed, offset, n, j) only, never on how the K samples are split into chunks; the batch uses
+   N K per / 4 counters.  eps != NULL: the chunk's (N, k, per) noise (parity runs).
+   temperature == 1 and K == 1: z has the bits of vcg_reparam_fwd on the same eps; temperature == 0: z[(n, j)] = mu[n] exactly.
+   16-byte loads and stores, grid-stride.  Refused (non-zero, vcg_last_error, nothing launched): mu, lv or z null; N, K or k < 1;
+   first < 0 or first + k > K; per == 0 or per % 4 != 0; temperature NaN, infinite or negative; a pointer not 16-byte aligned. */
+int vcg_reparam_many_fwd(const float* mu, const float* lv, const float* eps, float* eps_out, float* z, int N, int K, int first,
+                         int k, size_t per, float temperature, uint64_t seed, uint64_t offset, void* stream);
+/* Running statistics over samples (new: the reference has no inference path).  y: (N, k, pixels, 4) fp32, a decoder's output for
+   one chunk of k samples per frame in the networks' layout; mean, m2: (N, pixels, 4) fp32, the running mean and the running sum of
+   squared deviations of clamp(y, 0, 1) — the values the user sees.  Per element the samples j = 0 .. k - 1 are folded in that order
+   with Welford's update, continuing from `seen` samples already folded:
+     c = seen + j + 1;  d = x - mean;  mean += d / c;  m2 = fmaf(d, x - mean, m2)
+   seen == 0 initialises the statistics: mean and m2 are not read and need not be cleared.  One loop body and no compiler-chosen
+   contraction: an element's operation sequence is the same for every chunking, so K samples folded in one call or in several give
+   the same bits.  Channel 3 of y is not read and is written as 0.  One element is one lane's float4: no reduction, no atomics.
+   Refused: a null pointer; N or k < 1; seen < 0 or seen + k > 2^24; pixels == 0; a pointer not 16-byte aligned; mean == m2. */
+int vcg_sample_accumulate(const float* y, float* mean, float* m2, int N, int k, int seen, size_t pixels, void* stream);
+/* The spread map of `count` >= 2 folded samples (new: the reference has no inference path): per pixel of the window
+   (top, left, H, W) of m2, an (N, Hp, Wp, 4) buffer vcg_sample_accumulate filled,
+     s = sqrt((m2_0 + m2_1 + m2_2) / (3 (count - 1))),
+   the RMS over the three channels of the unbiased sample standard deviation, evaluated in double.  out_f32: (N, H, W) fp32, s
+   rounded once; out_u8: (N, H, W) uint8, floor(255 min(1, gain s) + 0.5); either may be NULL.  result[n]: the mean of s over image
+   n's window, fp32, accumulated in double: each 16 x 16 tile writes its partial to a slot of its own in ws and a final pass sums an
+   image's slots in a fixed order (csrc/metrics.hip's scheme) — no float atomics, and an image's result does not depend on the
+   batch it is in.  Nothing outside the window is read.
+   ws: vcg_spread_workspace(N, H, W) = N ceil(H / 16) ceil(W / 16) doubles rounded up to 16 bytes (0 and vcg_last_error for bad
+   sizes; host arithmetic), 16-byte aligned.
+   Refused: m2, result or ws null; count < 2; gain NaN, infinite or negative; N, H or W < 1; a window that leaves the buffer; m2 or
+   ws not 16-byte aligned, out_f32 or result not 4-byte aligned; a workspace that is too small. */
+size_t vcg_spread_workspace(int N, int H, int W);
+int vcg_spread_display_hw(const float* m2, int count, float gain, float* out_f32, unsigned char* out_u8, float* result, int N,
+                          int Hp, int Wp, int top, int left, int H, int W, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

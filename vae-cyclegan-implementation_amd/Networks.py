@@ -218,6 +218,14 @@ class VariationalEncoderBlock(nn.Module):
             object.__setattr__(self, "_pair", ops.FusedConvPair(self.muConv.conv, self.logvarConv[0].conv,
                                                                 ops.ConvSpec(in_channels, 2 * latent_dim, 3, 1, 1, True, 1)))
 
+    def latent(self, x):
+        """(mu, raw logvar) of `forward`'s convolutions, without the reparameterisation: no eps draw is consumed."""
+        x = ops.to_nhwc(x)
+        if ops.FUSE_MU_LOGVAR and self._pair is not None and x.is_cuda:
+            mu, lv0 = ops.conv_pair(x, self._pair)
+            return mu, self.logvarConv[1](lv0)
+        return self.muConv(x), self.logvarConv(x)
+
     def forward(self, x):
         x = ops.to_nhwc(x)
         if ops.FUSE_MU_LOGVAR and self._pair is not None and x.is_cuda:
@@ -695,6 +703,14 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         z, mu, logvar = self.variational_encoder_block(encoded)
         Gx = self.decoder(self.variational_decoder_block(z))
         return Gx, mu, logvar
+
+    def latent(self, x):
+        """The encoder half of `forward`: (mu, raw logvar) of x's latent distribution.  Draws no eps."""
+        return self.variational_encoder_block.latent(self.encoder(x))
+
+    def decode(self, z):
+        """The decoder half of `forward` on latents z (any batch)."""
+        return self.decoder(self.variational_decoder_block(z))
 
     def configure_optimizers(self, lr=1e-4, betas=(0.5, 0.999), clip_grad_norm=0.0, ema_decay=0.0, pool_size=0):
         return self._single_optimizer(self.parameters(), lr, betas, clip_grad_norm, ema_decay, pool_size)
@@ -1268,6 +1284,12 @@ class DoubleAutoencoder(_DoubleStep):
         return t, x, y
 
 
+def _side(side):
+    if side not in ("A", "B"):
+        raise ValueError(f"side must be 'A' or 'B', got {side!r}")
+    return side
+
+
 class DoubleVariationalAutoencoder(_DoubleStep):
     """Shared encoder, one VAE bottleneck and one decoder per modality — the pretraining model for CycleVAE / CycleVAEGAN
     (reference Networks.py:608-852).  eps draws per forward: block A on enc(x), then block B on enc(y); validation adds one
@@ -1326,6 +1348,16 @@ class DoubleVariationalAutoencoder(_DoubleStep):
     def translate_B_to_A(self, y):
         z, _, _ = self.vae_encoder_block_A(self.encoder(ops.to_nhwc(y)))
         return self.decoder_A(self.vae_decoder_block_A(z))
+
+    def latent(self, x, side):
+        """(mu, raw logvar) of the bottleneck a translation INTO modality `side` ("A" or "B") samples: translate_A_to_B reads block
+        B, translate_B_to_A block A.  Draws no eps."""
+        return getattr(self, "vae_encoder_block_" + _side(side)).latent(self.encoder(ops.to_nhwc(x)))
+
+    def decode(self, z, side):
+        """Latents z through the decoder block and decoder of modality `side`."""
+        side = _side(side)
+        return getattr(self, "decoder_" + side)(getattr(self, "vae_decoder_block_" + side)(z))
 
     def create_cycle_vae(self):
         """reference :701-736: G = encoder + VAE blocks B + decoder_B, F = encoder + VAE blocks A + decoder_A."""

@@ -42,6 +42,40 @@ struct VcgProfScope {
   ~VcgProfScope() { if (on) vcg_prof_end(st); }
 };
 
+// Philox4x32-10 + Box-Muller: the eps / synthetic-pixel stream of vcg_randn, vcg_rand_uniform and the reparameterisation kernels
+// (misc.hip, sample_stats.hip).  Counter `ctr` yields four values; one definition, so every kernel that draws at (seed, offset + q)
+// gets the same bits.
+struct Philox4 { uint32_t x, y, z, w; };
+__host__ __device__ static inline Philox4 philox4x32_10(uint64_t ctr, uint64_t key) {
+  uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0x243F6A88u, c3 = 0x85A308D3u;
+  uint32_t k0 = (uint32_t)key, k1 = (uint32_t)(key >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+    uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  Philox4 o = {c0, c1, c2, c3};
+  return o;
+}
+__device__ static inline float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+__device__ static inline void box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
+  float r = sqrtf(-2.0f * __logf(u01(a)));
+  float th = 6.283185307179586f * u01(b);
+  float s, c;
+  __sincosf(th, &s, &c);
+  n0 = r * c; n1 = r * s;
+}
+__device__ static inline float4 randn4(uint64_t seed, uint64_t quad) {
+  Philox4 r = philox4x32_10(quad, seed);
+  float4 o;
+  box_muller(r.x, r.y, o.x, o.y);
+  box_muller(r.z, r.w, o.z, o.w);
+  return o;
+}
+
 // division by a runtime constant: q = (umulhi(n, mul) + n) >> sh, valid for n < 2^31
 struct FastDiv {
   uint32_t d, mul, sh;

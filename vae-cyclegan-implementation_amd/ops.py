@@ -1486,3 +1486,90 @@ def image_metrics_hw(out, target, window=None):
     _native.check(_native.lib().vcg_image_metrics_hw(_ptr(op), _ptr(tp), _ptr(res), n, hp, wp, top, left, h, w, _ptr(ws),
                                                      ws.numel() * 4, _stream()), "vcg_image_metrics_hw")
     return res
+
+
+# ------------------------------------------------------------------ the sampling translator (translate.py --samples K)
+def _latent_phys(mu, logvar, what):
+    _require_gpu(mu, what)
+    _require_gpu(logvar, what)
+    if mu.dim() != 4 or mu.shape != logvar.shape:
+        raise RuntimeError(f"{what}: mu and logvar must be two (N, C, h, w) maps of one shape, got {tuple(mu.shape)} and {tuple(logvar.shape)}")
+    return as_phys(mu), as_phys(logvar)
+
+
+def reserve_eps_many(mu, samples):
+    """Reserve the eps draws of `samples` reparameterisations of every map of `mu` (logical (N, C, h, w)): the stream advances
+    once, by N * samples * per / 4 counters (per: floats of one physical map), and the position is returned for
+    `reparameterize_many(seed_offset=)`, whose chunks then draw inside the reservation."""
+    n, c, h, w = mu.shape
+    off = _RNG["offset"]
+    _RNG["offset"] += n * int(samples) * (h * w * pitch(c) // 4)
+    return off
+
+
+def reparameterize_many(mu, logvar, samples, first=0, count=None, eps=None, temperature=1.0, seed_offset=None):
+    """Inference only (no autograd node): the samples first .. first + count - 1 of the `samples` of every latent map,
+    z[(n, j)] = mu[n] + temperature * eps[(n, j)] * exp(0.5 * clamp(logvar[n], -10, 10)) -> (z, eps used), logical
+    (N * count, C, h, w) batches with sample j of map n at index n * count + (j - first): what a decoder takes.
+    eps: None draws on the device — sample (n, j) at `seed_offset` + (n * samples + j) * per / 4 of the ops stream, whatever the
+    chunking; `seed_offset` None reserves the whole batch here (reserve_eps_many) and is only allowed for a call that covers all
+    the samples.  eps given: the chunk's noise, logical (N, count, C, h, w) (parity runs); the stream does not move."""
+    mup, lvp = _latent_phys(mu, logvar, "reparameterize_many")
+    n, c, h, w = mu.shape
+    samples, first = int(samples), int(first)
+    count = samples - first if count is None else int(count)
+    per = h * w * pitch(c)
+    z = torch.empty((n * max(count, 0), h, w, pitch(c)), dtype=torch.float32, device=mu.device)
+    used = torch.empty_like(z)
+    epsp, off = None, 0
+    if eps is not None:
+        if tuple(eps.shape) != (n, count, c, h, w):
+            raise RuntimeError(f"reparameterize_many: eps has shape {tuple(eps.shape)}, expected {(n, count, c, h, w)}")
+        epsp = as_phys(eps.to(mu.device).reshape(n * count, c, h, w))
+    elif seed_offset is None:
+        if first != 0 or count != samples:
+            raise RuntimeError("reparameterize_many: a chunk of a batch needs the batch's seed_offset (ops.reserve_eps_many): the "
+                               "eps stream advances once per batch, not per chunk")
+        off = reserve_eps_many(mu, samples)
+    else:
+        off = int(seed_offset)
+    _native.check(_native.lib().vcg_reparam_many_fwd(_ptr(mup), _ptr(lvp), _ptr(epsp), _ptr(used), _ptr(z), n, samples, first, count, per,
+                                                     float(temperature), _RNG["seed"], off, _stream()), "vcg_reparam_many_fwd")
+    return logical_of(z, c), logical_of(used, c)
+
+
+def sample_accumulate(y, mean, m2, samples_in_chunk, seen):
+    """Fold a chunk of decoded samples into running statistics, in place (csrc/sample_stats.hip): y logical
+    (N * samples_in_chunk, 3, Hp, Wp) with sample j of frame n at index n * samples_in_chunk + j; mean, m2 logical (N, 3, Hp, Wp) nhwc
+    views (`logical_of(torch.empty((N, Hp, Wp, 4)), 3)`): Welford's mean and sum of squared deviations of clamp(y, 0, 1) after
+    `seen` + samples_in_chunk samples.  seen == 0 initialises them (they need not be cleared)."""
+    _require_gpu(y, "sample_accumulate")
+    k = int(samples_in_chunk)
+    for t, name in ((mean, "mean"), (m2, "m2")):
+        _require_gpu(t, "sample_accumulate")
+        if t.dim() != 4 or t.shape[1] != 3 or not is_nhwc_view(t):
+            raise RuntimeError(f"sample_accumulate: {name} must be a logical (N, 3, Hp, Wp) nhwc view, got shape {tuple(t.shape)}")
+    n, _, hp, wp = mean.shape
+    if mean.shape != m2.shape or k < 1 or tuple(y.shape) != (n * k, 3, hp, wp):
+        raise RuntimeError(f"sample_accumulate: y {tuple(y.shape)} is not {k} sample(s) of each of the {n} frames of mean "
+                           f"{tuple(mean.shape)} / m2 {tuple(m2.shape)}")
+    _native.check(_native.lib().vcg_sample_accumulate(_ptr(as_phys(y)), _ptr(phys_of(mean)), _ptr(phys_of(m2)), n, k, int(seen),
+                                                      hp * wp, _stream()), "vcg_sample_accumulate")
+    return mean, m2
+
+
+def spread_display_hw(m2, count, window=None, gain=2.0, uint8=False):
+    """The spread map of `count` >= 2 folded samples over `window` = (top, left, H, W) of m2 (logical (N, 3, Hp, Wp); None: the
+    whole image): per pixel the RMS over the channels of the unbiased sample standard deviation -> (map, per-image mean of the
+    map as (N,) fp32).  map: (N, H, W) fp32, with `uint8` the grey image floor(255 min(1, gain s) + 0.5), with uint8="both" the
+    pair (fp32, uint8) from the one launch."""
+    _require_gpu(m2, "spread_display_hw")
+    n, hp, wp, top, left, h, w = _window_of(m2, window, "spread_display_hw")
+    lib = _native.lib()
+    ws = torch.empty(max(lib.vcg_spread_workspace(n, h, w), 16) // 4, dtype=torch.float32, device=m2.device)
+    f32 = torch.empty((n, h, w), dtype=torch.float32, device=m2.device) if uint8 in (False, "both") else None
+    u8 = torch.empty((n, h, w), dtype=torch.uint8, device=m2.device) if uint8 in (True, "both") else None
+    res = torch.empty((n,), dtype=torch.float32, device=m2.device)
+    _native.check(lib.vcg_spread_display_hw(_ptr(as_phys(m2)), int(count), float(gain), _ptr(f32), _ptr(u8), _ptr(res), n, hp, wp, top,
+                                            left, h, w, _ptr(ws), ws.numel() * 4, _stream()), "vcg_spread_display_hw")
+    return ((f32, u8) if uint8 == "both" else u8 if uint8 else f32), res

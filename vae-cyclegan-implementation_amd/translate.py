@@ -12,6 +12,10 @@ whole-frame result; a batch above `ops.MAX_TRANSLATE_PIXELS` padded pixels is re
 Directions: `a2b` is G (the one generator of autoencoder / vae / aegan / vaegan), `b2a` is F of the cycle models.  For doubleae /
 doublevae the two directions are the models' `translate_A_to_B` (decoder_B) and `translate_B_to_A` (decoder_A) — NOT what
 test.py shows for them, which is the reconstruction decoder_A(encoder(x)) their forward returns first.
+
+`--samples K` (variational generators): K draws per frame from ONE encoder pass — the latent's mu and logvar do not depend on eps —
+decoded in chunks of as many samples as the pixel bound admits, with the running mean and the per-pixel spread of the draws
+accumulated on the device (csrc/sample_stats.hip; DESIGN.md, "Sampling translator").
 """
 import argparse
 import json
@@ -149,6 +153,110 @@ def translate_images(model, architecture, frames, direction="a2b", eps="sample",
     return ops.to_display_hw(y, window, uint8=not return_float)
 
 
+# ------------------------------------------------------------------ K draws per frame
+def sampler_of(model, architecture, direction="a2b"):
+    """(latent, decode) of one direction of a variational model: x -> (mu, logvar) and z -> translated batch, the two halves of
+    what `generator_of` returns.  Refuses what has no latent distribution to draw from."""
+    arch = train.ALIASES.get(architecture, architecture)
+    if arch in train.REFERENCE_ARCHS and arch not in VARIATIONAL:
+        raise ValueError(f"{arch} is not variational ({', '.join(VARIATIONAL)} are): its output is one image, there is nothing to sample")
+    generator_of(model, arch, direction)                            # unknown architecture, wrong direction
+    if arch == "vae":
+        return model.latent, model.decode
+    if arch == "doublevae":
+        side = "B" if direction == "a2b" else "A"
+        return (lambda x: model.latent(x, side)), (lambda z: model.decode(z, side))
+    gen = model.G if direction == "a2b" else model.F
+    return gen.latent, gen.decode
+
+
+def sample_chunks(n, hp, wp, samples, chunk=None):
+    """[(first, k)]: the samples 0 .. samples - 1 of n frames of hp x wp padded pixels in decoder batches of n * k images, k the
+    largest with n * k * hp * wp <= ops.MAX_TRANSLATE_PIXELS (`chunk`: at most this many)."""
+    if samples < 1 or n < 1 or n * hp * wp > ops.MAX_TRANSLATE_PIXELS:
+        raise ValueError(f"sample_chunks: {samples} sample(s) of {n} frame(s) of {hp}x{wp}")
+    if chunk is not None and chunk < 1:
+        raise ValueError(f"chunk must be at least 1, got {chunk}")
+    k = ops.MAX_TRANSLATE_PIXELS // (n * hp * wp)
+    k = min(k, samples) if chunk is None else min(k, samples, chunk)
+    return [(first, min(k, samples - first)) for first in range(0, samples, k)]
+
+
+def _check_sampling(samples, temperature):
+    if samples < 2:
+        raise ValueError(f"samples must be at least 2 (a spread needs two draws), got {samples}; one draw is translate_images")
+    if not (math.isfinite(temperature) and temperature >= 0):
+        raise ValueError(f"temperature must be finite and >= 0, got {temperature}")
+
+
+def sample_padded(model, architecture, x, window, samples, direction="a2b", temperature=1.0, eps=None, chunk=None, spread_gain=2.0,
+                  target=None, debug=False):
+    """`sample_images` on a loaded logical (N, 3, Hp, Wp) batch whose frames are `window` of it; the eps stream goes on where it
+    is.  `target` (a batch like x): adds "metrics" (N, 4) of the mean image and "sample_metrics" (N, K, 4), on the device."""
+    latent, decode = sampler_of(model, architecture, direction)
+    _check_sampling(samples, temperature)
+    n, _, hp, wp = x.shape
+    top, left, h, w = window
+    plan = sample_chunks(n, hp, wp, samples, chunk)
+    model.eval()
+    out = {}
+    with torch.no_grad():
+        mu, logvar = latent(x)                                      # the one encoder pass
+        if eps is None:
+            offset = ops.reserve_eps_many(mu, samples)              # the stream advances once per batch, not per chunk
+        elif tuple(eps.shape) != (n, samples) + tuple(mu.shape[1:]):
+            raise RuntimeError(f"eps has shape {tuple(eps.shape)}, expected {(n, samples) + tuple(mu.shape[1:])}")
+        else:
+            eps, offset = eps.to(x.device), None
+        drawn = torch.empty((n, samples, h, w, 3), dtype=torch.float32 if debug else torch.uint8, device=x.device)
+        mean = ops.logical_of(torch.empty((n, hp, wp, 4), dtype=torch.float32, device=x.device), 3)
+        m2 = ops.logical_of(torch.empty((n, hp, wp, 4), dtype=torch.float32, device=x.device), 3)
+        used, sample_metrics = [], []
+        for first, k in plan:
+            z, e = ops.reparameterize_many(mu, logvar, samples, first, k, eps=None if eps is None else eps[:, first:first + k],
+                                           temperature=temperature, seed_offset=offset)
+            y = decode(z)                                           # (N * k, 3, Hp, Wp), sample j of frame n at n * k + j
+            drawn[:, first:first + k] = ops.to_display_hw(y, window, uint8=not debug).view(n, k, h, w, 3)
+            ops.sample_accumulate(y, mean, m2, k, first)
+            if target is not None:
+                t = ops.logical_of(ops.as_phys(target).repeat_interleave(k, dim=0), 3)
+                sample_metrics.append(ops.image_metrics_hw(y, t, window).view(n, k, 4))
+            if debug:
+                used.append(e.reshape(n, k, *e.shape[1:]))
+        (spread, spread_u8), mean_spread = ops.spread_display_hw(m2, samples, window, gain=spread_gain, uint8="both")
+        out.update(samples=drawn, mean=ops.to_display_hw(mean, window, uint8=not debug), spread=spread, spread_u8=spread_u8,
+                   mean_spread=mean_spread)
+        if target is not None:
+            out.update(metrics=ops.image_metrics_hw(mean, target, window), sample_metrics=torch.cat(sample_metrics, dim=1))
+        if debug:
+            out["eps"] = torch.cat(used, dim=1)
+    return out
+
+
+def sample_images(model, architecture, frames, samples, direction="a2b", seed=1234, temperature=1.0, eps=None, chunk=None, device=None,
+                  spread_gain=2.0, debug=False):
+    """`samples` >= 2 translations of each uint8 frame (as translate_images takes them) by a variational generator, from one
+    encoder pass -> a dict of device tensors:
+      samples      uint8 (N, K, H, W, 3), sample j of frame n drawn with z = mu + temperature * eps[n, j] * sigma;
+      mean         uint8 (N, H, W, 3), the display conversion of the running mean of the clamped samples;
+      spread       fp32 (N, H, W), per pixel the RMS over the channels of the unbiased sample standard deviation;
+      spread_u8    uint8 (N, H, W), floor(255 min(1, spread_gain * spread) + 0.5);
+      mean_spread  fp32 (N,), the mean of `spread` per frame.
+    The decoder runs on chunks of samples (`sample_chunks`; `chunk` lowers the chunk size); a draw depends on (seed, n, j) only,
+    not on the chunking.  seed None: the eps stream goes on where it is.  eps: (N, K, latent, Hp / 16, Wp / 16) noise instead of
+    drawn one (parity runs).  debug: samples and mean as fp32 clamped to [0, 1], and "eps", the noise that was used."""
+    frames = _as_frames(frames)
+    n, h, w, _ = frames.shape
+    sampler_of(model, architecture, direction)                      # refusals come before anything is copied
+    _check_sampling(samples, temperature)
+    ops.check_translate_size(n, h, w)
+    device = device or next(model.parameters()).device
+    x, window = ops.image_load(frames.to(device, non_blocking=True))
+    if eps is None and seed is not None:
+        ops.manual_seed(seed)
+    return sample_padded(model, architecture, x, window, samples, direction, temperature, eps, chunk, spread_gain, debug=debug)
+
+
 # ------------------------------------------------------------------ files
 def discover_inputs(path):
     """The image files of `path` (one file, or the files of a directory in name order)."""
@@ -204,6 +312,23 @@ def output_name(path, suffix="_translated"):
     return f"{Path(path).stem}{suffix}.png"
 
 
+def sample_output_names(path, samples, suffix="_translated"):
+    """The PNGs --samples K writes for one input: the K draws, their mean, the spread map."""
+    stem = f"{Path(path).stem}{suffix}"
+    return {"samples": [f"{stem}_s{j:02d}.png" for j in range(samples)], "mean": f"{stem}_mean.png", "spread": f"{stem}_spread.png"}
+
+
+def checkpoint_architecture(checkpoint_or_run_dir, architecture=None):
+    """The architecture `load_generator` will build, without loading anything but a run directory's args.json."""
+    path = Path(checkpoint_or_run_dir)
+    if architecture is None and path.is_dir():
+        with open(path / "args.json") as f:
+            architecture = json.load(f)["architecture"]
+    if architecture is None:
+        raise ValueError("a bare checkpoint file needs --architecture (a run directory has it in args.json)")
+    return train.ALIASES.get(architecture, architecture)
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="Translate whole images of any size with a trained generator (MI355X-native path)")
     p.add_argument("--checkpoint", required=True, help="a run directory (args.json + best_model.pth) or a .pth file")
@@ -218,6 +343,16 @@ def build_parser():
     p.add_argument("--eps", choices=["sample", "mean"], default="sample",
                    help="variational generators: sample the latent (as test.py does) or decode its mean (deterministic)")
     p.add_argument("--seed", type=int, default=1234, help="the eps stream of --eps sample")
+    p.add_argument("--samples", type=int, default=1,
+                   help="variational generators: draw this many translations per frame from one encoder pass and write "
+                        "<stem><suffix>_s00.png ..., their mean <stem><suffix>_mean.png and the per-pixel spread <stem><suffix>_spread.png "
+                        "(grey).  1: one image per frame, as without the flag")
+    p.add_argument("--temperature", type=float, default=1.0,
+                   help="with --samples: scale of the latent noise, z = mu + T * eps * sigma (0 decodes the mean K times)")
+    p.add_argument("--spread_gain", type=float, default=2.0,
+                   help="with --samples: the spread PNG shows min(1, G * s).  The sample standard deviation s of K values in [0, 1] "
+                        "cannot exceed 0.5 sqrt(K / (K - 1)), so the default 2 saturates only near that theoretical maximum: it is "
+                        "derived, not tuned on a model, and a real model's maps are far darker — you will usually raise it")
     p.add_argument("--batch_size", type=int, default=1, help="frames of equal size are translated together, at most this many")
     p.add_argument("--size", type=int, default=None,
                    help="first resize every frame to SIZE x SIZE (the reference's Resize((S, S)); a multiple of 16, at least 32)")
@@ -285,6 +420,53 @@ def run_resized(model, architecture, paths, targets, args, device):
         done += x.shape[0]
 
 
+def _sampled_to_host(res, names):
+    """One batch of sample_padded on the host: per file (uint8 images, metric rows or None, mean spread)."""
+    u8 = {k: res[k].cpu().numpy() for k in ("samples", "mean", "spread_u8")}
+    spread = res["mean_spread"].cpu().double().numpy()
+    rows = res["metrics"].cpu().double().numpy() if "metrics" in res else None
+    srows = res["sample_metrics"].cpu().double().numpy() if "metrics" in res else None
+    return [dict(name=n, samples=u8["samples"][i], mean=u8["mean"][i], spread=u8["spread_u8"][i], mean_spread=float(spread[i]),
+                 metrics=None if rows is None else rows[i], sample_metrics=None if srows is None else srows[i])
+            for i, n in enumerate(names)]
+
+
+def run_batch_sampled(model, architecture, frames, targets, args, device):
+    """run_batch for --samples K: the batch's sample_padded result (the eps stream goes on where it is)."""
+    x, window = ops.image_load(frames.to(device, non_blocking=True))
+    t = ops.image_load(targets.to(device, non_blocking=True))[0] if targets is not None else None
+    return sample_padded(model, architecture, x, window, args.samples, args.direction, args.temperature, spread_gain=args.spread_gain,
+                         target=t)
+
+
+def run_resized_sampled(model, architecture, paths, targets, args, device):
+    """run_resized for --samples K: yields (paths of a batch, sample_padded result)."""
+    pipe = input_pipeline.DeviceInputPipeline(_PairFiles(paths, targets), args.batch_size, args.size, device, recipe="test",
+                                              shuffle=False, seed=args.seed, num_workers=max(1, args.num_workers),
+                                              same_xy=targets is None)
+    done = 0
+    for batch in pipe:
+        x = ops.to_nhwc(batch["x"])
+        n, _, hp, wp = x.shape
+        yield paths[done:done + n], sample_padded(model, architecture, x, (0, 0, hp, wp), args.samples, args.direction,
+                                                  args.temperature, spread_gain=args.spread_gain,
+                                                  target=ops.to_nhwc(batch["y"]) if targets is not None else None)
+        done += n
+
+
+def samples_report(files, with_metrics):
+    """--samples K: metrics.json in its usual shape for the MEAN images, each file with the K draws' metrics under "samples" and
+    its "mean_spread" (with --targets); otherwise samples.json with the mean spread per file."""
+    if not with_metrics:
+        return {"num_files": len(files), "per_file": {f["name"]: {"mean_spread": _finite_or_none(f["mean_spread"])} for f in files}}
+    rep = metrics_report([f["name"] for f in files], [f["metrics"] for f in files])
+    for f in files:
+        rep["per_file"][f["name"]]["samples"] = [{k: _finite_or_none(float(r[i])) for i, k in enumerate(METRIC_NAMES)}
+                                                 for r in f["sample_metrics"]]
+        rep["per_file"][f["name"]]["mean_spread"] = _finite_or_none(f["mean_spread"])
+    return rep
+
+
 def _finite_or_none(v):
     return float(v) if math.isfinite(v) else None
 
@@ -310,6 +492,19 @@ def main(argv=None):
         raise ValueError("--batch_size must be at least 1")
     if args.size is not None and (args.size < ops.MIN_TRANSLATE_SIDE or args.size % 16):
         raise ValueError(f"--size must be a multiple of 16 and at least {ops.MIN_TRANSLATE_SIDE}")
+    if args.samples < 1:
+        raise ValueError("--samples must be at least 1")
+    if args.samples >= 2:
+        if args.eps == "mean":
+            raise ValueError("--samples draws from the latent distribution: it cannot be combined with --eps mean (the mean has no spread)")
+        _check_sampling(args.samples, args.temperature)
+        if not (math.isfinite(args.spread_gain) and args.spread_gain >= 0):
+            raise ValueError(f"--spread_gain must be finite and >= 0, got {args.spread_gain}")
+        arch = checkpoint_architecture(args.checkpoint, args.architecture)
+        if arch not in VARIATIONAL:
+            raise ValueError(f"--samples needs a variational checkpoint ({', '.join(VARIATIONAL)}); {arch} has nothing to sample")
+    elif args.temperature != 1.0:
+        raise ValueError("--temperature scales the draws of --samples K: it needs --samples of at least 2")
     device = _device()
     model, architecture = load_generator(args.checkpoint, args.architecture, args.latent_dim, None, device, ema=args.ema)
     generator_of(model, architecture, args.direction)               # a direction the model does not have: fail before any file
@@ -343,13 +538,31 @@ def main(argv=None):
             print(f"  {p.name} -> {output_name(p, args.suffix)}")
         done[0] += len(batch_paths)
 
+    sampled = []
+
+    def write_sampled(batch_paths, res):
+        from PIL import Image
+        files = _sampled_to_host(res, [p.name for p in batch_paths])
+        jobs = []
+        for p, f in zip(batch_paths, files):
+            out_names = sample_output_names(p, args.samples, args.suffix)
+            jobs += list(zip(out_names["samples"], f["samples"])) + [(out_names["mean"], f["mean"]), (out_names["spread"], f["spread"])]
+            print(f"  {p.name} -> {out_names['samples'][0]} .. {out_names['samples'][-1]}, {out_names['mean']}, {out_names['spread']}")
+        list(pool.map(lambda job: Image.fromarray(job[1]).save(out_dir / job[0]), jobs))
+        sampled.extend(files)
+        done[0] += len(batch_paths)
+
     if args.size is not None:
         problem = size_problem(args.batch_size, args.size, args.size)
         if problem:
             raise ValueError(f"--size {args.size} with --batch_size {args.batch_size}: {problem}")
         targets = [target_of[p] for p in paths] if args.targets else None
-        for batch_paths, u8, metrics in run_resized(model, architecture, paths, targets, args, device):
-            write(batch_paths, u8, metrics)
+        if args.samples >= 2:
+            for batch_paths, res in run_resized_sampled(model, architecture, paths, targets, args, device):
+                write_sampled(batch_paths, res)
+        else:
+            for batch_paths, u8, metrics in run_resized(model, architecture, paths, targets, args, device):
+                write(batch_paths, u8, metrics)
     else:
         shapes = []
         for p in list(paths):
@@ -373,13 +586,18 @@ def main(argv=None):
             except (OSError, ValueError) as e:
                 skipped.extend((p, str(e)) for p in batch_paths)
                 continue
+            if args.samples >= 2:
+                write_sampled(batch_paths, run_batch_sampled(model, architecture, frames, targets, args, device))
+                continue
             u8, metrics = run_batch(model, architecture, frames, targets, args, device)
             write(batch_paths, u8, metrics)
     pool.shutdown()
-    if args.targets:
-        with open(out_dir / "metrics.json", "w") as f:
-            json.dump(metrics_report(names, rows), f, indent=2, allow_nan=False)
-        print(f"Saved metrics to: {out_dir / 'metrics.json'}")
+    if args.targets or args.samples >= 2:
+        report = out_dir / ("metrics.json" if args.targets else "samples.json")
+        with open(report, "w") as f:
+            json.dump(samples_report(sampled, bool(args.targets)) if args.samples >= 2 else metrics_report(names, rows), f, indent=2,
+                      allow_nan=False)
+        print(f"Saved metrics to: {report}")
     for p, why in skipped:
         print(f"Skipped {p}: {why}", file=sys.stderr)
     print(f"Translated {done[0]} file(s) into {out_dir}"
