@@ -260,6 +260,28 @@ int vcg_ssim_loss_fwd(const float* a, const float* b, float* out, int N, int H, 
    positions.  The coefficients are recomputed from a and b (a 20-pixel halo per 16 x 16 pixel tile): no workspace.  There is
    no gradient with respect to b. */
 int vcg_ssim_loss_bwd(const float* a, const float* b, const float* gout, float* ga, int N, int H, int W, void* stream);
+/* Gradient-matching loss (new: the reference has no edge term): an L1 on the horizontal and vertical finite differences of
+   d = a - b at S = `scales` in 1..4 subsampled scales (Eigen & Fergus 2015; Li & Snavely 2018).  With d_s[i, j] = d[i 2^s, j 2^s],
+   H_s = ceil(H / 2^s), W_s = ceil(W / 2^s), s = 0 .. S - 1, and the sums taken over the N images and the 3 logical channels:
+     X_s = sum |d_s[i, j+1] - d_s[i, j]| over i < H_s, j < W_s - 1,   M_sx = 3 N H_s (W_s - 1)
+     Y_s = sum |d_s[i+1, j] - d_s[i, j]| over i < H_s - 1, j < W_s,   M_sy = 3 N (H_s - 1) W_s
+     out[0] = 1 / S  sum_s (X_s / M_sx + Y_s / M_sy);  a direction with no pair (M = 0) contributes 0, the divisor stays S.
+   a (generated), b (target): (N, H, W, 4) fp32, the networks' layout, 16-byte aligned, channel 3 never read into a sum; H, W >= 1
+   independent.  ws: vcg_grad_loss_workspace(N, H, W, scales) bytes = N ceil(H / 32) ceil(W / 32) 2 scales doubles rounded up to
+   16 bytes (0 and vcg_last_error for bad sizes), 16-byte aligned: the 2 S partial sums of each 32 x 32 tile of pixels go to slots
+   of the tile's own and a final pass sums them in a fixed order — no float atomics, the same input gives the same bits.
+   csrc/grad_loss.hip. */
+size_t vcg_grad_loss_workspace(int N, int H, int W, int scales);
+int vcg_grad_loss_fwd(const float* a, const float* b, float* out, int N, int H, int W, int scales, void* ws, size_t ws_bytes,
+                      void* stream);
+/* ga = gout[0] * d loss / d a, (N, H, W, 4) with channel 3 = 0, written for every pixel; gout is read on the device.  The pixel
+   (y, x) belongs, at every scale s with 2^s | y and 2^s | x, to the pairs with its neighbours 2^s to the left, right, above and
+   below, where those lie inside the image:
+   ga(y, x) = gout / S sum_s [ (sgn(left pair) - sgn(right pair)) / M_sx + (sgn(upper pair) - sgn(lower pair)) / M_sy ],
+   a pair's sign that of (its right or lower pixel's d) - (its left or upper pixel's d), sgn(0) = 0.  No workspace.  There is no
+   gradient with respect to b. */
+int vcg_grad_loss_bwd(const float* a, const float* b, const float* gout, float* ga, int N, int H, int W, int scales,
+                      void* stream);
 /* out[0] = sum_i w[i]*(*s[i]) ; the composite loss lines Networks.py:941,2012-2018 */
 int vcg_lincomb_fwd(const float* const* s, const float* w, int count, float* out, void* stream);
 

@@ -1,7 +1,7 @@
 """Atomic losses with the reference's class surface (Losses.py:14-121 of the reference),
 each reduction a HIP kernel (wavefront shuffle -> block partial -> ordered final sum).
 
-Only the six atomic classes (and StructuralLoss, which the reference lacks) exist here: the reference's composite loss classes
+Only the six atomic classes (and StructuralLoss and GradientMatchingLoss, which the reference lacks) exist here: the reference's composite loss classes
 (Losses.py:123-379) are dead code there and are not part of the training step.
 """
 import torch.nn as nn
@@ -36,6 +36,21 @@ class StructuralLoss(nn.Module):
 
     def forward(self, generated, target):
         return ops.ssim_loss(generated, target)
+
+
+class GradientMatchingLoss(nn.Module):
+    """Multi-scale gradient matching (Eigen & Fergus 2015; Li & Snavely 2018): the mean absolute horizontal and vertical finite
+    difference of generated - target, averaged over `scales` in 1..4 scales, scale s keeping every 2^s-th pixel of both axes
+    (new: the reference has no edge term)."""
+
+    def __init__(self, scales=4):
+        super().__init__()
+        if isinstance(scales, bool) or int(scales) != scales or not 1 <= int(scales) <= 4:
+            raise ValueError(f"scales must be an integer in 1..4, got {scales!r}")
+        self.scales = int(scales)
+
+    def forward(self, generated, target):
+        return ops.grad_match_loss(generated, target, self.scales)
 
 
 class GANLossGenerator(nn.Module):

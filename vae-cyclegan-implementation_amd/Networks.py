@@ -19,8 +19,8 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .Losses import (CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss, StructuralLoss,
-                     KLDivergenceLoss, TranslationLoss)
+from .Losses import (CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, GradientMatchingLoss, IdentityLoss,
+                     StructuralLoss, KLDivergenceLoss, TranslationLoss)
 from .image_pool import ImagePool, pool_seed as _pool_seed
 from .optim import FusedAdam
 
@@ -397,6 +397,15 @@ def _structural(kwargs):
     return lam, (StructuralLoss() if lam > 0.0 else None)
 
 
+def _grad_matching(kwargs):
+    """(lambda_grad, GradientMatchingLoss(grad_scales) or None) of a configure_loss call, as _structural: with the weight at its
+    default 0 no loss object exists and the step computes, launches and reports exactly what it did before the term was added."""
+    lam = float(kwargs.get("lambda_grad", 0.0))
+    if lam < 0.0:
+        raise ValueError(f"lambda_grad must be >= 0, got {lam}")
+    return lam, (GradientMatchingLoss(kwargs.get("grad_scales", 4)) if lam > 0.0 else None)
+
+
 def _backward_and_step(loss, optimizer, reducer):
     """zero_grad -> backward -> [data-parallel gradient exchange, its buckets launched from inside the backward] -> step."""
     optimizer.zero_grad()
@@ -599,6 +608,8 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         self.loss_fn = None
         self.loss_ssim_fn = None
         self.lambda_ssim = 0.0
+        self.loss_grad_fn = None
+        self.lambda_grad = 0.0
         self.apply(self._init_weights)
 
     def _init_weights(self, module):
@@ -614,6 +625,18 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
     def configure_loss(self, **kwargs):
         self.loss_fn = TranslationLoss()
         self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
+        self.lambda_grad, self.loss_grad_fn = _grad_matching(kwargs)
+
+    def _extra_terms(self, output, y):
+        """The optional terms beside the L1, in the order they are reported: {name: device scalar} and their weights."""
+        extra, weights = {}, []
+        if getattr(self, "loss_ssim_fn", None) is not None:     # (a caller's stand-in for `self` need not know the terms)
+            extra["loss_ssim"] = self.loss_ssim_fn(output, y)
+            weights.append(self.lambda_ssim)
+        if getattr(self, "loss_grad_fn", None) is not None:
+            extra["loss_grad"] = self.loss_grad_fn(output, y)
+            weights.append(self.lambda_grad)
+        return extra, weights
 
     def training_step(self, batch):
         """Written out (no _report): the reference's NaN / Inf guard reads the loss on the host before the update, and the plain
@@ -626,10 +649,10 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         output = self(x)
         loss_trans = self.loss_fn(output, y)
-        G_loss, loss_ssim = loss_trans, None
-        if getattr(self, "loss_ssim_fn", None) is not None:     # (a caller's stand-in for `self` need not know the term)
-            loss_ssim = self.loss_ssim_fn(output, y)
-            G_loss = ops.weighted_sum([loss_trans, loss_ssim], [1.0, self.lambda_ssim])
+        G_loss = loss_trans
+        extra, weights = Autoencoder._extra_terms(self, output, y)
+        if extra:
+            G_loss = ops.weighted_sum([loss_trans, *extra.values()], [1.0, *weights])
         value = float(G_loss.detach())                 # the reference's isnan/isinf guard syncs here too (:357)
         bad = math.isnan(value) or math.isinf(value)
         red = self.grad_reducer
@@ -641,17 +664,16 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
             print("NaN or Inf detected in loss during training step; skipping the update.")
             self.optimizer.zero_grad()
             m = {"nan_detected": True, "G_loss": float("nan"), "loss_trans": float("nan"), "total_loss": float("nan")}
-            if loss_ssim is not None:
-                m["loss_ssim"] = float("nan")
+            m.update({k: float("nan") for k in extra})
             if getattr(self.optimizer, "clip_state", None) is not None:      # skipped here, on the host, before any gradient existed
                 m["grad_norm"], m["grad_skipped"] = float("nan"), 1.0
             return m
         _backward_and_step(G_loss, self.optimizer, red)
         clip = _clip_scalars(**{"": self.optimizer})
-        if loss_ssim is not None:
-            m = _metrics_to_host({"G_loss": G_loss, "loss_trans": loss_trans, "loss_ssim": loss_ssim, **clip}, red)
-            out = {"G_loss": m["G_loss"], "loss_trans": m["loss_trans"], "total_loss": m["G_loss"], "loss_ssim": m["loss_ssim"]}
-            out.update({k: m[k] for k in clip})
+        if extra:
+            m = _metrics_to_host({"G_loss": G_loss, "loss_trans": loss_trans, **extra, **clip}, red)
+            out = {"G_loss": m["G_loss"], "loss_trans": m["loss_trans"], "total_loss": m["G_loss"]}
+            out.update({k: m[k] for k in (*extra, *clip)})
             return out
         if red is not None or clip:
             m = _metrics_to_host({"loss_trans": loss_trans, **clip}, red)
@@ -667,11 +689,11 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         with torch.no_grad():
             x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
             output = self(x)
-            if self.loss_ssim_fn is not None:
-                loss_trans, loss_ssim = self.loss_fn(output, y), self.loss_ssim_fn(output, y)
-                t = {"G_loss": ops.weighted_sum([loss_trans, loss_ssim], [1.0, self.lambda_ssim]), "loss_trans": loss_trans,
-                     "loss_ssim": loss_ssim}
-                return _report(self, t, (("G_loss", "G_loss"), ("total_loss", "G_loss")) + _same("loss_trans", "loss_ssim") + _GX,
+            if self.loss_ssim_fn is not None or self.loss_grad_fn is not None:
+                loss_trans = self.loss_fn(output, y)
+                extra, weights = self._extra_terms(output, y)
+                t = {"G_loss": ops.weighted_sum([loss_trans, *extra.values()], [1.0, *weights]), "loss_trans": loss_trans, **extra}
+                return _report(self, t, (("G_loss", "G_loss"), ("total_loss", "G_loss")) + _same("loss_trans", *extra) + _GX,
                                False, Gx=output)
             value = float(self.loss_fn(output, y))
             return {"G_loss": value, "total_loss": value, "loss_trans": value, "Gx": output}
@@ -691,8 +713,10 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self.loss_trans_fn = None
         self.loss_kl_fn = None
         self.loss_ssim_fn = None
+        self.loss_grad_fn = None
         self.lambda_kl = 0
         self.lambda_ssim = 0.0
+        self.lambda_grad = 0.0
         self.apply(self._init_weights)
 
     def _init_weights(self, module):
@@ -720,6 +744,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self.loss_kl_fn = KLDivergenceLoss()
         self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
         self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
+        self.lambda_grad, self.loss_grad_fn = _grad_matching(kwargs)
 
     def _check_configured(self):
         if self.optimizer is None:
@@ -730,7 +755,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             raise ValueError("KL divergence loss function has not been configured yet.")
 
     def _losses(self, batch):
-        """-> (G(x), the step's scalars in the order they are reported: G_loss, loss_trans, loss_kl, [loss_ssim])"""
+        """-> (G(x), the step's scalars in the order they are reported: G_loss, loss_trans, loss_kl, [loss_ssim], [loss_grad])"""
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         output, mu, logvar = self(x)
         loss_trans = self.loss_trans_fn(output, y)
@@ -741,6 +766,10 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             named["loss_ssim"] = self.loss_ssim_fn(output, y)
             terms.append(named["loss_ssim"])
             weights.append(self.lambda_ssim)
+        if self.loss_grad_fn is not None:
+            named["loss_grad"] = self.loss_grad_fn(output, y)
+            terms.append(named["loss_grad"])
+            weights.append(self.lambda_grad)
         named["G_loss"] = ops.weighted_sum(terms, weights)
         return output, named
 
@@ -895,6 +924,8 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         self.loss_kl = None
         self.loss_ssim = None
         self.lambda_ssim = 0.0
+        self.loss_grad = None
+        self.lambda_grad = 0.0
         # data-parallel hook: set by parallel.attach(); called as reducer(phase, optimizer)
         self.grad_reducer = None
 
@@ -938,6 +969,7 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
         self.lambda_ssim, self.loss_ssim = _structural(kwargs)
+        self.lambda_grad, self.loss_grad = _grad_matching(kwargs)
 
     def _check_configured(self, need_opt=True):
         if (self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None
@@ -999,6 +1031,10 @@ class CycleVAEGAN(_GanMixin, nn.Module):
             t["loss_ssim"] = ops.weighted_sum([self.loss_ssim(FGx, x), self.loss_ssim(GFy, y)], [1.0, 1.0])
             terms.append(t["loss_ssim"])
             weights.append(self.lambda_ssim)
+        if self.loss_grad is not None:               # the gradient-matching cycle term, on the structural term's operands
+            t["loss_grad"] = ops.weighted_sum([self.loss_grad(FGx, x), self.loss_grad(GFy, y)], [1.0, 1.0])
+            terms.append(t["loss_grad"])
+            weights.append(self.lambda_grad)
         t["G_loss"] = ops.weighted_sum(terms, weights)
         # discriminator objective on the SAME discriminator outputs (reference :2038-2040)
         t["D_loss_x_real"], _ = ops.mse_const(DXx, 1.0)
@@ -1020,6 +1056,8 @@ class CycleVAEGAN(_GanMixin, nn.Module):
             keys += ("loss_identity",)
         if self.loss_ssim is not None:
             keys += ("loss_ssim",)
+        if self.loss_grad is not None:
+            keys += ("loss_grad",)
         return (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + (() if training else _GX_FY)
 
     def _pooled_d_terms(self, t, Gx, Fy):

@@ -1116,6 +1116,53 @@ def ssim_loss(generated, target):
     return _SsimLossFn.apply(generated, target)
 
 
+class _GradLossFn(torch.autograd.Function):
+    """Multi-scale gradient-matching loss of (generated, target) (csrc/grad_loss.hip); the gradient reaches `generated` only."""
+
+    @staticmethod
+    def forward(ctx, a, b, scales):
+        lib = _native.lib()
+        if a.shape != b.shape:
+            raise RuntimeError(f"grad_match_loss: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
+        if a.dim() != 4 or a.shape[1] != 3:
+            raise RuntimeError(f"grad_match_loss: expected (N, 3, H, W) images, got shape {tuple(a.shape)}")
+        ap, bp = as_phys(a), as_phys(b)
+        n, h, w, _ = ap.shape
+        out = torch.empty((), dtype=torch.float32, device=a.device)
+        need = lib.vcg_grad_loss_workspace(n, h, w, scales)
+        if need == 0:
+            _native.check(-1, "vcg_grad_loss_workspace")
+        ws = workspace(need, a.device)
+        _native.check(lib.vcg_grad_loss_fwd(_ptr(ap), _ptr(bp), _ptr(out), n, h, w, scales, _ptr(ws), ws.numel() * 4, _stream()),
+                      "vcg_grad_loss_fwd")
+        ctx.save_for_backward(ap, bp)             # the backward takes its signs from the two images
+        ctx.scales = scales
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        lib = _native.lib()
+        ap, bp = ctx.saved_tensors
+        n, h, w, _ = ap.shape
+        g = g.contiguous()
+        ga = torch.empty_like(ap)
+        _native.check(lib.vcg_grad_loss_bwd(_ptr(ap), _ptr(bp), _ptr(g), _ptr(ga), n, h, w, ctx.scales, _stream()),
+                      "vcg_grad_loss_bwd")
+        return logical_of(ga, 3), None, None
+
+
+def grad_match_loss(generated, target, scales=4):
+    """Mean |horizontal and vertical finite differences of generated - target| over `scales` in 1..4 subsampled scales of
+    (N, 3, H, W) images, H, W >= 1: a 0-dim fp32 tensor.  `target` is an input image: no gradient."""
+    if isinstance(scales, bool) or int(scales) != scales or not 1 <= int(scales) <= 4:
+        raise RuntimeError(f"grad_match_loss: scales must be an integer in 1..4, got {scales!r}")
+    if target.requires_grad:
+        raise RuntimeError("grad_match_loss: the target must not require a gradient (only d loss / d generated is computed)")
+    return _GradLossFn.apply(generated, target, int(scales))
+
+
 class _MseConstFn(torch.autograd.Function):
     """nn.MSELoss()(d, full_like(d, target)) and d.mean(); Losses.py:80-81,99-100, Networks.py:2048-2051."""
 

@@ -42,6 +42,7 @@ REFERENCE_ARCHS = ["autoencoder", "doubleae", "doublevae", "vae", "aegan", "vaeg
                    "cycleaegan", "cyclevaegan"]
 BUILT = tuple(REFERENCE_ARCHS)
 SSIM_ARCHS = ("autoencoder", "vae", "cycleaegan", "cyclevaegan")     # the models whose configure_loss takes lambda_ssim
+GRAD_ARCHS = SSIM_ARCHS                # ... and lambda_grad / grad_scales: the term sits wherever the structural one does
 
 
 def create_model(architecture, paired=True, latent_dim=64):
@@ -195,6 +196,17 @@ def clip_bound(text):
     return value
 
 
+def grad_weight(text):
+    """argparse type of --lambda_grad: a finite weight >= 0 (0: off)."""
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not math.isfinite(value) or value < 0.0:
+        raise argparse.ArgumentTypeError(f"--lambda_grad must be finite and >= 0 (0: the term is not computed), got {text}")
+    return value
+
+
 def ema_decay_value(text):
     """argparse type of --ema_decay: a finite decay in [0, 1) (0: off)."""
     try:
@@ -243,6 +255,11 @@ def build_parser():
     p.add_argument("--lambda_recon", type=float, default=1.0)
     p.add_argument("--lambda_ssim", type=float, default=0.0,
                    help="weight of the structural term 1 - SSIM beside the L1 (" + ", ".join(SSIM_ARCHS) + "); 0: not computed")
+    p.add_argument("--lambda_grad", type=grad_weight, default=0.0,
+                   help="weight of the multi-scale gradient-matching term (an L1 on the finite differences of generated - target) "
+                        "beside the L1 (" + ", ".join(GRAD_ARCHS) + "); 0: not computed")
+    p.add_argument("--grad_scales", type=int, default=4, choices=(1, 2, 3, 4),
+                   help="number of scales of the gradient-matching term; scale s keeps every 2^s-th pixel")
     p.add_argument("--clip_grad_norm", type=clip_bound, default=0.0,
                    help="clip each optimizer's gradient to this global 2-norm inside the fused Adam step (every architecture); "
                         "a step whose gradient holds a NaN / Inf is skipped; 0: off")
@@ -328,7 +345,16 @@ def main(args):
     if getattr(args, "lambda_ssim", 0.0) != 0.0 and args.architecture not in SSIM_ARCHS:
         raise ValueError(f"--lambda_ssim is supported by {', '.join(SSIM_ARCHS)} only, not by {args.architecture}: "
                          "the flag would be ignored")
-    clip = getattr(args, "clip_grad_norm", 0.0)           # (an args object built without the parser)
+    lambda_grad = getattr(args, "lambda_grad", 0.0)       # (an args object built without the parser)
+    if not math.isfinite(lambda_grad) or lambda_grad < 0.0:
+        raise ValueError(f"--lambda_grad must be finite and >= 0 (0: the term is not computed), got {lambda_grad}")
+    if lambda_grad != 0.0 and args.architecture not in GRAD_ARCHS:
+        raise ValueError(f"--lambda_grad is supported by {', '.join(GRAD_ARCHS)} only, not by {args.architecture}: "
+                         "the flag would be ignored")
+    grad_scales = getattr(args, "grad_scales", 4)
+    if grad_scales not in (1, 2, 3, 4):
+        raise ValueError(f"--grad_scales must be 1, 2, 3 or 4, got {grad_scales}")
+    clip = getattr(args, "clip_grad_norm", 0.0)
     if not math.isfinite(clip) or clip < 0.0:
         raise ValueError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {clip}")
     ema_decay = getattr(args, "ema_decay", 0.0)
@@ -396,7 +422,7 @@ def main(args):
         print(f"Averaged generator weights (decay {ema_decay}): the test loss, and with it best_model.pth, is the averaged weights'")
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
                          lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
-                         lambda_ssim=getattr(args, "lambda_ssim", 0.0))
+                         lambda_ssim=getattr(args, "lambda_ssim", 0.0), lambda_grad=lambda_grad, grad_scales=grad_scales)
     if world > 1:
         parallel.attach(model)
     same_xy = args.architecture in ("autoencoder", "vae")
