@@ -33,7 +33,7 @@
                       their maps are 2 x 2 .. 4 x 4 and run the fp32 kernels).  (1, 64) / (1, 32) is the smallest such pair:
                       32 is the smallest side the networks take (ops.MIN_TRANSLATE_SIDE) and no spec changes its answer between
                       64 and 128 or 256.  After A the side-stream repack_async has written the pack WITHOUT the fp32 Wf block
-                      (ops.LAZY_WF, ops.OVERLAP_ENABLED are asserted); B must rebuild it in place on the main stream, and the
+                      (ops.OVERLAP_ENABLED is asserted); B must rebuild it in place on the main stream, and the
                       rebuilt pack then serves A again.  In the order B, A, B the need is known from the first step on
                       (`_need_wf` is sticky) and every pack carries the block.
    deferral           vae, A = (2, 64), B = (3, 32), A.  consumer_takes_deferred = vcg_conv_pre_ok and kept forward state:
@@ -220,7 +220,7 @@ def _reads_wf(pkg, model, n, size):
 def _takes_deferred(pkg, model, n, size):
     """consumer_takes_deferred of a training forward, from the library's answers themselves (no cache of the spec involved)"""
     lib = pkg._native.lib()
-    assert pkg.ops.DEFER_NORM and pkg.ops.KEEP_FORWARD_STATE
+    assert pkg.ops.DEFER_NORM
     return {name: bool(lib.vcg_conv_pre_ok(spec.desc(*g))) and int(lib.vcg_conv_saved_floats(spec.desc(*g))) > 0
             for name, spec, g in _conv_geoms(pkg, model, n, size)}
 
@@ -296,7 +296,7 @@ WF_A, WF_B = (1, 64), (1, 32)
 @pytest.mark.parametrize("order", ["A,B,A", "B,A,B"])
 def test_a_geometry_that_reads_wf_after_one_that_does_not(order, pkg, device):
     ops = pkg.ops
-    assert ops.LAZY_WF and ops.OVERLAP_ENABLED
+    assert ops.OVERLAP_ENABLED
     model = _first(pkg, device, "autoencoder")
     at_a, at_b = _reads_wf(pkg, model, *WF_A), _reads_wf(pkg, model, *WF_B)
     late = [name for name in at_a if at_a[name] == 0 and at_b[name] == 1]

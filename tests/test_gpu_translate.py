@@ -392,11 +392,10 @@ def test_pad_and_crop_is_what_it_says(pkg, tr):
 @pytest.mark.parametrize("first,second", [((96, 160), (256, 256)), ((256, 256), (48, 80))])
 @pytest.mark.parametrize("arch", ["autoencoder", "vae"])
 def test_sizes_that_change_between_calls(pkg, tr, arch, first, second):
-    """A, B, A on one model with the default lazy-Wf packs: the third call gives the first one's bits, and each result is that
+    """A, B, A on one model with its lazy-Wf packs: the third call gives the first one's bits, and each result is that
     of a model that has seen nothing else.  96x160 -> 256x256 -> 96x160 is the sequence a user meets; 256x256 -> 48x80 is the
     order in which the first geometry leaves the fp32 Wf block out of most packs (every 3x3 layer of the 16x16 bottleneck runs
     from its planes) and the second one reads it (3x5 maps take the direct kernels): a pack that is not rebuilt is caught here."""
-    assert pkg.ops.LAZY_WF
     model = _fresh(pkg, arch, seed=21)
     fa, fb = _frames(1, first[0], first[1], 3, 45), _frames(1, second[0], second[1], 3, 46)
     run = lambda m, f: tr.translate_images(m, arch, f, seed=9, return_float=True)

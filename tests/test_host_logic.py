@@ -852,3 +852,53 @@ def test_operand_range_bound_rejects_broken_splits():
         ref, tol = A.double() @ B.double(), gemm_bound(A, B)
         assert worst(emulate_gemm(A, B, a_shift=2, a_amax=src_amax)) <= 1.0, f"K = {K}: shift 2 leaves the bound"
         assert worst(emulate_gemm(A, B, a_shift=1, a_amax=src_amax)) > 1.0, f"K = {K}: the bound does not see a shift of 1 for 2"
+
+
+def _environment_names_read(path):
+    """Names of the environment variables the source file at `path` reads: the first argument of every `os.environ.get` /
+    `.setdefault` / `.pop` / `os.getenv` call and every `os.environ[...]` subscript (`os` under any alias)."""
+    import ast
+    tree = ast.parse(open(path).read(), path)
+
+    def is_environ(node):
+        return isinstance(node, ast.Attribute) and node.attr == "environ" and isinstance(node.value, ast.Name)
+
+    names = set()
+    for node in ast.walk(tree):
+        key = None
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute):
+            if (is_environ(node.func.value) and node.func.attr in ("get", "setdefault", "pop")) or \
+                    (node.func.attr == "getenv" and isinstance(node.func.value, ast.Name)):
+                key = node.args[0]
+        elif isinstance(node, ast.Subscript) and is_environ(node.value):
+            key = node.slice
+        if key is not None:
+            assert isinstance(key, ast.Constant) and isinstance(key.value, str), \
+                f"{path}:{node.lineno}: an environment variable whose name is not a string literal"
+            names.add(key.value)
+    return names
+
+
+def test_the_package_reads_only_the_listed_environment_variables():
+    """Every switch the Python package reads from the environment, by name.  A/B switches whose question is settled are
+    retired, not kept; a new one has to be added here on purpose."""
+    import glob
+    listed = {
+        # the launcher's (torchrun) and the runtime's
+        "RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR",
+        "HIP_FORCE_DEV_KERNARG", "GPU_MAX_HW_QUEUES", "HSA_ENABLE_IPC_MODE_LEGACY",
+        # the build and the library that is loaded
+        "HIPCC", "VCG_LIBVCG",
+        # streams (bench.py and tools/*.sh drive them)
+        "VCG_WGRAD_OVERLAP", "VCG_DIR_STREAMS",
+        # data parallelism
+        "VCG_BUCKET_MB", "VCG_DP_FROM_BACKWARD", "VCG_DP_LAUNCH_STREAM", "VCG_NCCL_PRIORITY",
+        # input pipeline
+        "VCG_HYPERSIM_ALIGNED",
+    }
+    sources = sorted(glob.glob(os.path.join(ROOT, "vae-cyclegan-implementation_amd", "*.py")))
+    assert sources
+    read = set()
+    for path in sources:
+        read |= _environment_names_read(path)
+    assert read == listed, f"read but not listed: {sorted(read - listed)}; listed but not read: {sorted(listed - read)}"

@@ -792,19 +792,14 @@ def _vae_pair(vae_a, a, ticket_a, vae_b, b, ticket_b, fork):
     """vae_a(a) on the caller's stream and vae_b(b) on `fork`'s second stream, issued alternately in half-generator pieces
     (encoder | bottleneck + decoder): the second stream has work after a quarter of the host time a whole generator takes to
     issue, and — autograd replays in reverse issue order — the backward alternates between the two chains at the same
-    granularity instead of one whole generator at a time (CycleVAEGAN step 32.54 -> 31.89 ms; block by block, through generator
-    coroutines, measured no better: 32.4 vs 32.3).  VCG_DIR_INTERLEAVE=0: whole generators."""
+    granularity instead of one whole generator at a time (against whole generators alternating between the streams, three
+    alternations: CycleVAEGAN step 32.54 / 32.64 / 34.36 -> 31.89 / 31.98 / 33.41 ms; block by block, through generator
+    coroutines, measured no better: 32.4 vs 32.3)."""
     def tail(vae, enc, ticket):                  # VariationalAutoencoder.forward after its encoder
         with ops.use_ticket(ticket):
             z, mu, lv = vae.variational_encoder_block(enc)
         return vae.decoder(vae.variational_decoder_block(z)), mu, lv
 
-    if not ops.DIR_INTERLEAVE:
-        with ops.use_ticket(ticket_a):
-            ra = vae_a(a)
-        with fork.second(), ops.use_ticket(ticket_b):
-            rb = vae_b(b)
-        return ra, rb
     ea = vae_a.encoder(a)
     with fork.second():
         eb = vae_b.encoder(b)
@@ -816,11 +811,6 @@ def _vae_pair(vae_a, a, ticket_a, vae_b, b, ticket_b, fork):
 
 def _ae_pair(ae_a, a, ae_b, b, fork):
     """The same for two plain autoencoders."""
-    if not ops.DIR_INTERLEAVE:
-        ra = ae_a(a)
-        with fork.second():
-            rb = ae_b(b)
-        return ra, rb
     ea = ae_a.encoder(a)
     with fork.second():
         eb = ae_b.encoder(b)

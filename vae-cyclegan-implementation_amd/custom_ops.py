@@ -11,20 +11,20 @@ module is the same block WITHOUT them, for every other caller:
   * registered with the dispatcher (`torch.library.custom_op`), with fake (shape-only) implementations and
     `register_autograd`, so `torch.compile` / `make_fx` trace through a model that uses it as one opaque node per block and
     `torch.library.opcheck` can test the registration (tests/test_custom_ops.py);
-  * the same C-ABI entry points underneath (include/vcg.h: vcg_conv_fwd_in_h, vcg_in_apply_h, vcg_in_bwd_h, vcg_act_bwd_h,
-    vcg_conv_wgrad_saved_h, vcg_conv_dgrad_h) — no second implementation, and no CPU path: a CPU tensor raises.
+  * the same call sequence underneath — `ops.conv_forward`, `norm_apply`, `block_dt`, `conv_wgrad`, `conv_dgrad`, the one place
+    each C-ABI entry point of the block is called from, here with no magnitude handle and no kept forward state — so no second
+    implementation, and no CPU path: a CPU tensor raises.
 
 The block is the reference's `Conv2d(reflect) [+ ReLU / Sigmoid] [+ InstanceNorm2d [+ ReLU] [+ residual] [+ PixelShuffle]]`
 (/root/reference/Networks.py:83-96 CaSb, :98-116 D, :118-131 U, :60-81 R); arguments as `ops.ConvSpec`.
 """
-import ctypes
 from collections import OrderedDict
 from typing import Optional, Tuple
 
 import torch
 from torch import Tensor
 
-from . import _native, ops
+from . import ops
 
 _SPECS = OrderedDict()          # geometry -> ConvSpec (descriptor builder only: nothing about a weight is cached here)
 _SPECS_MAX = 512
@@ -86,42 +86,19 @@ def conv_block_op(x: Tensor, weight: Tensor, bias: Optional[Tensor], residual: O
     """-> (out, t, mean, rstd).  `out`: the block's result, a logical (N, C, H, W) tensor in the package's NHWC storage
     (`ops.to_nchw_contiguous` converts).  `t` (the conv output the InstanceNorm saw), `mean`, `rstd`: what the backward needs
     — empty when `norm` is false (then `out` itself is what the activation's backward reads)."""
-    lib = _native.lib()
+    if not norm and (residual is not None or shuffle or post_act):
+        raise RuntimeError("vcg::conv_block: residual / shuffle / post_act need norm=True")
     spec = _spec_for(weight, stride, pad, reflect, ups, epi_act, norm, post_act, shuffle)
     _geometry(x, weight, stride, pad, ups, norm, shuffle)
     xp = ops.as_phys(x)
     n, h, w, _ = xp.shape
-    ho, wo = spec.out_hw(h, w)
-    cd = spec.desc(n, h, w)
-    dev = x.device
-    wf = _fresh_pack(spec, weight, (n, h, w))
-    c = spec.cout_pitch
-    t = torch.empty((n, ho, wo, c), dtype=torch.float32, device=dev)
-    none = ctypes.c_void_p(0)
-    if norm:
-        mean = torch.empty((n, c), dtype=torch.float32, device=dev)
-        rstd = torch.empty((n, c), dtype=torch.float32, device=dev)
-        ws = ops.workspace(lib.vcg_conv_fwd_in_workspace(cd), dev)
-        _native.check(lib.vcg_conv_fwd_in_h(ops._ptr(xp), ops._ptr(wf), ops._ptr(bias), ops._ptr(t), ops._ptr(mean), ops._ptr(rstd),
-                                            ops.IN_EPS, none, cd, ops._ptr(ws), ws.numel() * 4, 0, ops._stream()), "vcg_conv_fwd_in")
-        resp = ops.as_phys(residual) if residual is not None else None
-        if shuffle:
-            outp = torch.empty((n, 2 * ho, 2 * wo, c // 4), dtype=torch.float32, device=dev)
-            cout_log = spec.cout // 4
-        else:
-            outp = torch.empty((n, ho, wo, c), dtype=torch.float32, device=dev)
-            cout_log = spec.cout
-        amax = ctypes.c_uint64(0)
-        _native.check(lib.vcg_in_apply_h(ops._ptr(t), ops._ptr(mean), ops._ptr(rstd), ops._ptr(resp), ops._ptr(outp), n, ho, wo, c,
-                                         post_act, int(shuffle), ctypes.byref(amax), ops._stream()), "vcg_in_apply")
-        return ops.logical_of(outp, cout_log), t, mean, rstd
-    if residual is not None or shuffle or post_act:
-        raise RuntimeError("vcg::conv_block: residual / shuffle / post_act need norm=True")
-    ws = ops.workspace(lib.vcg_conv_fwd_workspace(cd), dev)
-    _native.check(lib.vcg_conv_fwd_in_h(ops._ptr(xp), ops._ptr(wf), ops._ptr(bias), ops._ptr(t), none, none, ops.IN_EPS, none, cd,
-                                        ops._ptr(ws), ws.numel() * 4, 0, ops._stream()), "vcg_conv_fwd_in")
-    e = torch.empty(0, dtype=torch.float32, device=dev)
-    return ops.logical_of(t, spec.cout), e, torch.empty_like(e), torch.empty_like(e)
+    t, mean, rstd = ops.conv_forward(spec, spec.desc(n, h, w), _fresh_pack(spec, weight, (n, h, w)), bias, xp, want_stats=norm)
+    if not norm:
+        e = torch.empty(0, dtype=torch.float32, device=x.device)
+        return ops.logical_of(t, spec.cout), e, torch.empty_like(e), torch.empty_like(e)
+    resp = ops.as_phys(residual) if residual is not None else None
+    outp, cout_log, _ = ops.norm_apply(t, mean, rstd, post_act, spec.cout, resp, shuffle)
+    return ops.logical_of(outp, cout_log), t, mean, rstd
 
 
 @conv_block_op.register_fake
@@ -142,48 +119,26 @@ def conv_block_backward_op(g: Tensor, x: Tensor, weight: Tensor, out: Tensor, t:
     """-> (dx, dweight, dbias) of `conv_block` for the output gradient `g` (the residual's gradient is `g` itself); tensors not
     asked for come back empty.  dbias of a block whose InstanceNorm follows the convolution directly (epi_act 0) is exactly
     zero — the mean subtraction cancels the bias — and is returned as zeros."""
-    lib = _native.lib()
     spec = _spec_for(weight, stride, pad, reflect, ups, epi_act, norm, post_act, shuffle)
     xp = ops.as_phys(x)
     n, h, w, _ = xp.shape
-    ho, wo = spec.out_hw(h, w)
     cd = spec.desc(n, h, w)
     dev = x.device
-    c = spec.cout_pitch
-    gp = ops.as_phys(g)
-    hnd = ctypes.c_uint64(0)
-    if norm:
-        dt = torch.empty_like(t)
-        ws = ops.workspace(lib.vcg_in_workspace(n, ho * wo, c), dev)
-        _native.check(lib.vcg_in_bwd_h(ops._ptr(gp), ops._ptr(t), ops._ptr(mean), ops._ptr(rstd), ops._ptr(dt), n, ho, wo, c, epi_act,
-                                       post_act, int(shuffle), ops._ptr(ws), ws.numel() * 4, ctypes.byref(hnd), ops._stream()), "vcg_in_bwd")
-    elif epi_act != ops.ACT_NONE:
-        tp = ops.as_phys(out)
-        dt = torch.empty_like(tp)
-        _native.check(lib.vcg_act_bwd_h(ops._ptr(gp), ops._ptr(tp), ops._ptr(dt), tp.numel(), epi_act, ctypes.byref(hnd), ops._stream()),
-                      "vcg_act_bwd")
-    else:
-        dt = gp
+    # without a norm the activation's backward reads the activation's output, which is `out`
+    dt, _ = ops.block_dt(spec, ops.as_phys(g), t if norm else ops.as_phys(out), mean, rstd)
     e = torch.empty(0, dtype=torch.float32, device=dev)
     dw, db, dx = e, torch.empty_like(e), torch.empty_like(e)
     if need_dw or need_db:
         gw = torch.zeros(weight.shape, dtype=torch.float32, device=dev)
         gb = torch.zeros(spec.cout, dtype=torch.float32, device=dev)
         cancels = norm and epi_act == ops.ACT_NONE
-        ws = ops.workspace(lib.vcg_conv_wgrad_workspace(cd), dev)
-        _native.check(lib.vcg_conv_wgrad_saved_h(ops._ptr(xp), ops._ptr(dt), ops._ptr(gw), None if cancels else ops._ptr(gb),
-                                                 ctypes.c_void_p(0), cd, ops._ptr(ws), ws.numel() * 4, 0, 0, ops._stream()), "vcg_conv_wgrad")
+        ops.conv_wgrad(cd, xp, dt, gw, None if cancels else gb)
         if need_dw:
             dw = gw
         if need_db:
             db = gb
     if need_dx:
-        wf = _fresh_pack(spec, weight, (n, h, w))
-        dxp = torch.empty_like(xp)
-        ws = ops.workspace(lib.vcg_conv_dgrad_workspace(cd), dev)
-        _native.check(lib.vcg_conv_dgrad_h(ops._ptr(dt), ops._ptr(wf), ops._ptr(dxp), cd, ops._ptr(ws), ws.numel() * 4, 0, ops._stream()),
-                      "vcg_conv_dgrad")
-        dx = ops.logical_of(dxp, spec.cin_phys_log)
+        dx = ops.logical_of(ops.conv_dgrad(cd, dt, _fresh_pack(spec, weight, (n, h, w))), spec.cin_phys_log)
     return dx, dw, db
 
 

@@ -71,10 +71,13 @@ class _timed:
 _WS = {}
 
 
+def _device_index(device):
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
 def workspace(nbytes, device):
     """One stream-ordered scratch buffer per (device, stream), grown on demand."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    key = (idx, torch.cuda.current_stream(device).cuda_stream)
+    key = (_device_index(device), torch.cuda.current_stream(device).cuda_stream)
     buf = _WS.get(key)
     if buf is None or buf.numel() * 4 < nbytes:
         n = max(int(nbytes * 1.25) // 4 + 64, 1 << 20)
@@ -93,13 +96,17 @@ _OVERLAP = [False]
 OVERLAP_ENABLED = os.environ.get("VCG_WGRAD_OVERLAP", "1") != "0"     # what `backward_overlapped` does; off = one stream
 
 
-def _side_stream(device):
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    st = _SIDE.get(idx)
+def _stream_of(table, device):
+    """The auxiliary stream `table` (_SIDE, _DIR, _LAUNCH) holds for `device`, created at first use."""
+    idx = _device_index(device)
+    st = table.get(idx)
     if st is None:
-        st = torch.cuda.Stream(device=device)
-        _SIDE[idx] = st
+        st = table[idx] = torch.cuda.Stream(device=device)
     return st
+
+
+def _side_stream(device):
+    return _stream_of(_SIDE, device)
 
 
 def join_side_streams():
@@ -120,7 +127,6 @@ def join_side_streams():
 # weights carry events (`ConvSpec.packed`, `FusedConvPair.tensors`), the images' magnitudes are measured before the fork
 # (`premeasure`).  VCG_DIR_STREAMS=0: one chain after the other, as in rounds 1-3.
 DIRECTION_STREAMS = os.environ.get("VCG_DIR_STREAMS", "1") != "0"
-DIR_INTERLEAVE = os.environ.get("VCG_DIR_INTERLEAVE", "1") != "0"       # 0: whole generators alternate between the two streams (A/B)
 _DIR = {}
 
 
@@ -130,14 +136,9 @@ def two_directions():
 
 class DirectionFork:
     def __init__(self, device):
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        st = _DIR.get(idx)
-        if st is None:
-            st = torch.cuda.Stream(device=device)
-            _DIR[idx] = st
-        self.second_stream = st
+        self.second_stream = _stream_of(_DIR, device)
         self.main = torch.cuda.current_stream(device)
-        st.wait_stream(self.main)                # everything issued so far (inputs, zeroed gradients, the optimizer's writes)
+        self.second_stream.wait_stream(self.main)   # everything issued so far (inputs, zeroed gradients, the optimizer's writes)
 
     def second(self):
         """Context: issue on the second chain's stream (no wait: the chains are independent after the fork)."""
@@ -153,12 +154,7 @@ _LAUNCH = {}
 def launch_stream(device):
     """The stream parallel.GradReducer issues its collectives under (it waits for a bucket's producer streams; nothing but RCCL
     waits for it)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    st = _LAUNCH.get(idx)
-    if st is None:
-        st = torch.cuda.Stream(device=device)
-        _LAUNCH[idx] = st
-    return st
+    return _stream_of(_LAUNCH, device)
 
 
 def create_streams(device):
@@ -175,8 +171,8 @@ def create_streams(device):
 def premeasure(t):
     """Publish the largest magnitude of `t` now, on the current stream, unless a valid handle is already on it: a tensor that
     two streams will read must not be measured by one of them after they have forked."""
-    if AMAX_HANDLES and t.is_cuda and not _amax_of(t):
-        _amax_tag(t, _measured_amax(as_phys(t)))
+    if t.is_cuda and not _amax_of(t):
+        _amax_tag(t, _measured_amax(t, logical=True))
 
 
 class wgrad_overlap:
@@ -276,6 +272,33 @@ def to_nhwc(x):
 
 
 # ------------------------------------------------------------------ conv block
+def _param_key(p):
+    """What a copy derived from parameter `p` (a weight pack, the fused mu / logvar weights) is valid for: parameters owned by a
+    FusedAdam carry that optimizer's step counter (`_vcg_epoch`), so a step of one optimizer does not invalidate what was
+    derived from another's parameters."""
+    ep = getattr(p, "_vcg_epoch", None)
+    return (ep[0] if ep is not None else PARAM_EPOCH[0], id(ep), p._version, p.data_ptr())
+
+
+class _WrittenOn:
+    """Where and when a buffer that several streams read was last written: the writer `mark`s, a reader on another stream
+    waits for that event (`order_reader`); a reader on the writer's stream is ordered already."""
+
+    def __init__(self):
+        self.stream = self.event = None
+
+    def mark(self, device):
+        self.stream = torch.cuda.current_stream(device)
+        self.event = torch.cuda.Event()
+        self.event.record(self.stream)
+
+    def order_reader(self, device):
+        if self.event is not None:
+            cur = torch.cuda.current_stream(device)
+            if cur != self.stream:
+                cur.wait_event(self.event)
+
+
 class ConvSpec:
     """Static description of one conv (+ fused activation / InstanceNorm / shuffle) block."""
 
@@ -293,8 +316,7 @@ class ConvSpec:
         self.cout_pitch = pitch(cout)
         self._packed = None
         self._packed_key = None
-        self._pack_stream = None
-        self._pack_event = None
+        self._pack_written = _WrittenOn()
         self._pack_weight = None
         self._need_wf = False            # some geometry this spec has run at reads the fp32 Wf block of the pack (sticky)
         self._wf_packed = False          # the current pack holds it
@@ -315,18 +337,18 @@ class ConvSpec:
 
     def packed(self, weight, geom=None):
         """Packed weight buffer (Wf + the transformed copies) for the current parameter values: repacked once per
-        optimizer step.  Parameters owned by a FusedAdam carry that optimizer's step counter (`_vcg_epoch`), so a step
-        of one optimizer does not invalidate the packs of another's parameters.
+        optimizer step (`_param_key`).
         `geom` = (n, h, w) of the call that is about to use the pack: the fp32 Wf block is only written for specs some
         geometry of which reads it (include/vcg.h, vcg_conv_reads_wf: the D / R / U layers run from their planes in every
-        direction — a third of the pack traffic of a step).  No geometry given (tests, `repack_async`): what is known so far."""
+        direction — a third of the pack traffic of a step; against packs that always carry it, same box twice: 36.82 / 36.74 ->
+        36.61 / 36.64 ms per step, -0.55 ms of side-stream pack kernels, -1 GB).  No geometry given (tests, `repack_async`):
+        what is known so far."""
         if geom is not None and geom not in self._geoms_seen:
             self._geoms_seen.add(geom)
-            if LAZY_WF and not self._need_wf and _native.lib().vcg_conv_reads_wf(self.desc(*geom)):
+            if not self._need_wf and _native.lib().vcg_conv_reads_wf(self.desc(*geom)):
                 self._need_wf = True
-        want_wf = self._need_wf or not LAZY_WF or not self._geoms_seen       # never used through a geometry yet: the full pack
-        ep = getattr(weight, "_vcg_epoch", None)
-        key = (ep[0] if ep is not None else PARAM_EPOCH[0], id(ep), weight._version, weight.data_ptr())
+        want_wf = self._need_wf or not self._geoms_seen       # never used through a geometry yet: the full pack
+        key = _param_key(weight)
         if self._packed is None or self._packed_key != key or self._packed.device != weight.device or (want_wf and not self._wf_packed):
             cd = self.desc(1, max(self.ups * self.k, 2 * self.ups * (self.pad + 1)), max(self.ups * self.k, 2 * self.ups * (self.pad + 1)))
             cd[14] = 0 if want_wf else 1                                   # VCG_CD_PACK_FLAGS
@@ -341,15 +363,11 @@ class ConvSpec:
             _native.check(_native.lib().vcg_pack_weight(_ptr(w), _ptr(self._packed), cd, _stream()), "vcg_pack_weight")
             self._wf_packed = want_wf
             self._packed_key = key
-            self._pack_stream = torch.cuda.current_stream(weight.device)
-            self._pack_event = torch.cuda.Event()
-            self._pack_event.record(self._pack_stream)
+            self._pack_written.mark(weight.device)
             self._pack_weight = weakref.ref(weight)
             _PACKS[id(self)] = self
-        elif self._pack_stream is not None:
-            cur = torch.cuda.current_stream(weight.device)
-            if cur != self._pack_stream:          # packed ahead of time on the side stream (repack_async): order after it
-                cur.wait_event(self._pack_event)
+        else:
+            self._pack_written.order_reader(weight.device)      # packed ahead of time on the side stream (repack_async)
         return self._packed
 
 
@@ -379,8 +397,11 @@ def repack_async(params):
 
 
 # Hand the largest magnitude of an activation / gradient from the kernel that wrote it to the convolution that reads it
-# (include/vcg.h, vcg_amax_hint).  VCG_AMAX_HANDLES=0: every convolution measures its operands itself (A/B measurements).
-AMAX_HANDLES = os.environ.get("VCG_AMAX_HANDLES", "1") != "0"
+# (include/vcg.h, vcg_amax_hint).  False (an A/B run or a test sets the attribute): every convolution measures its operands itself.
+# Consulted by `_amax_of`, `_measured_amax` and `_amax_out` below and nowhere else: with handles off they deal in 0, "unknown",
+# which `_amax_tag`, every caller and the library already take.
+AMAX_HANDLES = True
+
 
 def _amax_tag(t, handle):
     """Leave `handle` on tensor object `t`, keyed on what it describes: the contents of this storage at this version.  torch bumps
@@ -411,24 +432,21 @@ def _amax_of(t):
     return handle
 
 
-def _measured_amax(t):
+def _measured_amax(t, logical=False):
     """Handle of the largest magnitude of a tensor no kernel published one for (an image, a latent, the gradient a loss hands
     down): measured ONCE on the current stream — the forward and the weight gradient that re-reads x, the weight and the data
     gradient of one dy, two convolutions of one input all take the handle instead of a pass each (round 3: 128 -> ~75 k_absmax
-    launches per step).  0 (the consumers measure) when handles are off."""
+    launches per step).  0 (the consumers measure) when handles are off.  `logical`: t is a logical (N, C, H, W) tensor."""
     if not AMAX_HANDLES:
         return 0
+    if logical:
+        t = as_phys(t)
     return int(_native.lib().vcg_amax_measure(_ptr(t), t.numel(), _stream()))
 
 
-# VCG_BIAS_IN_BWD=0: bias gradients of the conv -> act -> InstanceNorm blocks from a pass of their own over dt (A/B measurements)
-BIAS_IN_BWD = os.environ.get("VCG_BIAS_IN_BWD", "1") != "0"
-
-# VCG_LAZY_WF=0: every pack carries the fp32 Wf block, read or not (A/B measurements)
-LAZY_WF = os.environ.get("VCG_LAZY_WF", "1") != "0"
-
-# Keep the forward's Winograd-transformed input for the weight gradient (VCG_KEEP_FORWARD_STATE=0: recompute it, as round 1 did)
-KEEP_FORWARD_STATE = os.environ.get("VCG_KEEP_FORWARD_STATE", "1") != "0"
+def _amax_out(cell):
+    """The handle a kernel returned through the pointer to `cell` (a c_uint64) — 0 when handles are off."""
+    return cell.value if AMAX_HANDLES else 0
 
 
 # Data parallelism: parallel.GradReducer.note — told about every weight gradient the backward has issued (and on which
@@ -479,14 +497,121 @@ def _grad_buffer(param):
     return g
 
 
+# ------------------------------------------------------------------ the conv block's library calls, each written once
+# Mechanism only ("One call site per library call of the conv block"): plain functions over PHYSICAL tensors that
+# allocate their outputs, issue one group of library calls on the current stream inside its `_timed` bracket and return the
+# results.  Operand magnitudes come in and go out as bare handles (0: unknown, the kernels measure).  What decides about
+# tensor tags, deferral, the kept forward state, streams, parameters and hooks is `_ConvBlockFn`; `custom_ops` is the same
+# sequence with none of that.  `flops`, `tag` = `conv_cost(...)`: what the bracket of a convolution reports.
+def conv_cost(spec, n, h, w):
+    """(algorithmic flops, tag) of one direction of `spec` on an (n, h, w) input."""
+    ho, wo = spec.out_hw(h, w)
+    return (2.0 * n * ho * wo * spec.cout * spec.k * spec.k * spec.cin,
+            f"{n}x{h}x{w}x{spec.cin_pitch}->{spec.cout_pitch} k{spec.k} s{spec.stride} u{spec.ups}")
+
+
+def conv_forward(spec, cd, wf, bias, xp=None, x_amax=0, lazy=None, want_stats=False, saved=None, flops=0.0, tag=""):
+    """The convolution (+ bias, + epilogue activation) of `xp`, whose largest magnitude handle `x_amax` names — or, with
+    `lazy` = (t_prev, mean, rstd, act, ...), of the producer's raw output normalised in this convolution's own gather — and, if
+    `want_stats`, the statistics of the InstanceNorm that follows, out of the conv's own epilogue where its launch plan allows
+    (csrc/conv_igemm.hip, vcg_conv_fwd_in).  `saved`: buffer for the forward state the weight gradient reuses, or None.
+    -> (t, mean, rstd); the last two None without statistics."""
+    lib = _native.lib()
+    n, (ho, wo), c, dev = cd[0], spec.out_hw(cd[1], cd[2]), spec.cout_pitch, wf.device
+    t = torch.empty((n, ho, wo, c), dtype=torch.float32, device=dev)
+    mean = rstd = None
+    if want_stats:
+        mean = torch.empty((n, c), dtype=torch.float32, device=dev)
+        rstd = torch.empty((n, c), dtype=torch.float32, device=dev)
+    with _timed("conv_fwd", flops, tag):
+        ws = workspace((lib.vcg_conv_fwd_in_workspace if want_stats else lib.vcg_conv_fwd_workspace)(cd), dev)
+        if lazy is not None:
+            _native.check(lib.vcg_conv_fwd_in_pre(_ptr(lazy[0]), _ptr(lazy[1]), _ptr(lazy[2]), lazy[3], _ptr(wf), _ptr(bias),
+                                                  _ptr(t), _ptr(mean), _ptr(rstd), IN_EPS, _ptr(saved), cd, _ptr(ws),
+                                                  ws.numel() * 4, _stream()), "vcg_conv_fwd_in_pre")
+        else:
+            _native.check(lib.vcg_conv_fwd_in_h(_ptr(xp), _ptr(wf), _ptr(bias), _ptr(t), _ptr(mean), _ptr(rstd), IN_EPS,
+                                                _ptr(saved), cd, _ptr(ws), ws.numel() * 4, x_amax, _stream()), "vcg_conv_fwd_in")
+    return t, mean, rstd
+
+
+def norm_out(t, cout, shuffle=False):
+    """Storage for the InstanceNorm's result on the raw conv output `t` of `cout` logical channels -> (outp, logical channels)."""
+    if not shuffle:
+        return torch.empty_like(t), cout
+    n, ho, wo, c = t.shape
+    return torch.empty((n, 2 * ho, 2 * wo, c // 4), dtype=torch.float32, device=t.device), cout // 4
+
+
+def norm_apply(t, mean, rstd, act, cout, resp=None, shuffle=False, outp=None):
+    """act((t - mean) * rstd) (+ residual `resp`), stored pixel-shuffled if `shuffle`, into `outp` (default: fresh storage).
+    -> (outp, logical channels, handle of its largest magnitude)."""
+    if outp is None:
+        outp, cout = norm_out(t, cout, shuffle)
+    n, ho, wo, c = t.shape
+    amax = ctypes.c_uint64(0)
+    with _timed("in_fwd"):
+        _native.check(_native.lib().vcg_in_apply_h(_ptr(t), _ptr(mean), _ptr(rstd), _ptr(resp), _ptr(outp), n, ho, wo, c, act,
+                                                   int(shuffle), ctypes.byref(amax), _stream()), "vcg_in_apply")
+    return outp, cout, _amax_out(amax)
+
+
+def block_dt(spec, gp, t, mean, rstd, gb=None):
+    """The gradient at the convolution's output from the block's output gradient `gp`: through the InstanceNorm (+ both
+    activations), through the epilogue activation alone (`t` is then the activation's output), or `gp` itself.  `gb`: a bias
+    gradient buffer to accumulate dt's column sums into in the same pass (vcg_in_bwd_bias), or None: not taken here.
+    -> (dt, handle of its largest magnitude: 0 for a passed-through gp)."""
+    lib = _native.lib()
+    if not spec.norm and spec.epi_act == ACT_NONE:
+        return gp, 0
+    dt = torch.empty_like(t)
+    h = ctypes.c_uint64(0)
+    if not spec.norm:
+        _native.check(lib.vcg_act_bwd_h(_ptr(gp), _ptr(t), _ptr(dt), t.numel(), spec.epi_act, ctypes.byref(h), _stream()), "vcg_act_bwd")
+        return dt, _amax_out(h)
+    n, ho, wo, c = t.shape
+    ws = workspace(lib.vcg_in_workspace(n, ho * wo, c), t.device)
+    with _timed("in_bwd"):
+        if gb is not None:
+            _native.check(lib.vcg_in_bwd_bias(_ptr(gp), _ptr(t), _ptr(mean), _ptr(rstd), _ptr(dt), n, ho, wo, c,
+                                              spec.epi_act, spec.post_act, int(spec.shuffle), _ptr(gb), spec.cout,
+                                              _ptr(ws), ws.numel() * 4, ctypes.byref(h), _stream()), "vcg_in_bwd_bias")
+        else:
+            _native.check(lib.vcg_in_bwd_h(_ptr(gp), _ptr(t), _ptr(mean), _ptr(rstd), _ptr(dt), n, ho, wo, c,
+                                           spec.epi_act, spec.post_act, int(spec.shuffle), _ptr(ws), ws.numel() * 4,
+                                           ctypes.byref(h), _stream()), "vcg_in_bwd")
+    return dt, _amax_out(h)
+
+
+def conv_wgrad(cd, xp, dt, gw, gb, saved=None, x_amax=0, dt_amax=0, flops=0.0, tag=""):
+    """Accumulate the weight gradient into `gw` and, unless `gb` is None, the bias gradient (dt's column sums) into `gb`;
+    `saved`: the forward state `conv_forward` kept, or None (recomputed)."""
+    lib = _native.lib()
+    ws = workspace(lib.vcg_conv_wgrad_workspace(cd), dt.device)
+    with _timed("conv_wgrad", flops, tag):
+        _native.check(lib.vcg_conv_wgrad_saved_h(_ptr(xp), _ptr(dt), _ptr(gw), _ptr(gb), _ptr(saved), cd, _ptr(ws),
+                                                 ws.numel() * 4, x_amax, dt_amax, _stream()), "vcg_conv_wgrad")
+
+
+def conv_dgrad(cd, dt, wf, dt_amax=0, flops=0.0, tag=""):
+    """-> the gradient at the convolution's (physical) input."""
+    lib = _native.lib()
+    dxp = torch.empty((cd[0], cd[1], cd[2], cd[3]), dtype=torch.float32, device=dt.device)
+    with _timed("conv_dgrad", flops, tag):
+        ws = workspace(lib.vcg_conv_dgrad_workspace(cd), dt.device)
+        _native.check(lib.vcg_conv_dgrad_h(_ptr(dt), _ptr(wf), _ptr(dxp), cd, _ptr(ws), ws.numel() * 4, dt_amax,
+                                           _stream()), "vcg_conv_dgrad")
+    return dxp
+
+
 # ------------------------------------------------------------------ deferred InstanceNorm (the fused Conv + IN + act hand-off)
 # A block whose only consumer is the next block's convolution can hand over its RAW conv output with the statistics instead of the
 # normalised tensor: `conv_block(..., defer=True)` returns a tensor whose storage is allocated but NOT written, tagged with
 # (t, mean, rstd, post_act); a `conv_block` that receives it normalises inside its own input gather (include/vcg.h,
 # vcg_conv_fwd_in_pre) where that exists for its geometry, and otherwise fills the storage first (`materialize`) — so every
 # conv_block consumer is correct either way, and nothing else may be handed a deferred tensor (Networks.py defers only between
-# the blocks of one Encoder / inside R).  VCG_DEFER_NORM=0: never defer (A/B measurements).
-DEFER_NORM = os.environ.get("VCG_DEFER_NORM", "1") != "0"
+# the blocks of one Encoder / inside R).  False (an A/B run or a test sets the attribute): never defer.
+DEFER_NORM = True
 
 
 def _lazy_of(x):
@@ -505,15 +630,9 @@ def materialize(x):
     if tag is None:
         return x
     t, mean, rstd, act, _, _ = tag
-    xp = phys_of(x)
-    n, h, w, c = xp.shape
-    amax = ctypes.c_uint64(0)
-    with _timed("in_fwd"):
-        _native.check(_native.lib().vcg_in_apply_h(_ptr(t), _ptr(mean), _ptr(rstd), None, _ptr(xp), n, h, w, c, act, 0,
-                                                   ctypes.byref(amax), _stream()), "vcg_in_apply")
+    _, _, amax = norm_apply(t, mean, rstd, act, x.shape[1], outp=phys_of(x))
     del x._vcg_lazy
-    if AMAX_HANDLES:
-        _amax_tag(x, amax.value)
+    _amax_tag(x, amax)
     return x
 
 
@@ -529,7 +648,7 @@ def consumer_takes_deferred(spec, n, h, w, needs_wgrad=True):
         cd = spec.desc(n, h, w)
         ok = bool(lib.vcg_conv_pre_ok(cd)), int(lib.vcg_conv_saved_floats(cd)) > 0
         cache[(n, h, w)] = ok
-    return ok[0] and (ok[1] and KEEP_FORWARD_STATE or not needs_wgrad)
+    return ok[0] and (ok[1] or not needs_wgrad)
 
 
 class _ConvBlockFn(torch.autograd.Function):
@@ -541,81 +660,48 @@ class _ConvBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, residual, spec, wparam, bparam, defer=False):
-        lib = _native.lib()
+        if not spec.norm and (residual is not None or spec.shuffle or spec.post_act):
+            raise RuntimeError("residual/shuffle/post_act need norm=True")
+        if defer and (residual is not None or spec.shuffle):
+            raise RuntimeError("a block with a residual or a shuffled store cannot defer its InstanceNorm")
+        # (grad mode is off inside Function.forward: needs_input_grad[1] says whether a backward for the weight will come)
+        wants_wgrad = wparam is not None and wparam.requires_grad and ctx.needs_input_grad[1]
         lazy = _lazy_of(x)
-        if lazy is not None:
-            xs = x.shape
-            wants_wgrad = wparam is not None and wparam.requires_grad and ctx.needs_input_grad[1]
-            if not consumer_takes_deferred(spec, xs[0], xs[2], xs[3], wants_wgrad):
-                materialize(x)
-                lazy = None
+        if lazy is not None and not consumer_takes_deferred(spec, x.shape[0], x.shape[2], x.shape[3], wants_wgrad):
+            materialize(x)
+            lazy = None
         xp = as_phys(x)
         n, h, w, pin = xp.shape
         if pin != spec.cin_pitch:
             raise RuntimeError(f"conv block expected {spec.cin_phys_log} input channels (pitch {spec.cin_pitch}), got pitch {pin}")
-        ho, wo = spec.out_hw(h, w)
         cd = spec.desc(n, h, w)
         wf = spec.packed(weight, (n, h, w))
-        dev = x.device
-        t = torch.empty((n, ho, wo, spec.cout_pitch), dtype=torch.float32, device=dev)
-        flops = 2.0 * n * ho * wo * spec.cout * spec.k * spec.k * spec.cin
-        tag = f"{n}x{h}x{w}x{spec.cin_pitch}->{spec.cout_pitch} k{spec.k} s{spec.stride} u{spec.ups}"
-        mean = rstd = saved = None
+        flops, tag = conv_cost(spec, n, h, w)
         # operand magnitudes (include/vcg.h): the block that wrote x left a handle to its largest magnitude on the tensor; the
         # kernels scale x by it instead of measuring x again (0: unknown, they measure)
-        x_amax = _amax_of(x) if lazy is None else 0
-        if not x_amax and AMAX_HANDLES and lazy is None:
-            x_amax = _measured_amax(xp)
-            _amax_tag(x, x_amax)              # a second convolution of this very tensor object (mu and logvar read one map)
-        out_amax = ctypes.c_uint64(0)
-        # forward state the weight gradient can reuse (the Winograd-transformed input V: 4x the activation — HBM is 288 GB)
-        # (grad mode is off inside Function.forward: needs_input_grad[1] says whether a backward for the weight will come)
-        if wparam is not None and wparam.requires_grad and ctx.needs_input_grad[1] and KEEP_FORWARD_STATE:
-            nsv = int(lib.vcg_conv_saved_floats(cd))
+        x_amax = 0
+        if lazy is None:
+            x_amax = _amax_of(x)
+            if not x_amax:
+                x_amax = _measured_amax(xp)
+                _amax_tag(x, x_amax)          # a second convolution of this very tensor object (mu and logvar read one map)
+        # forward state the weight gradient reuses (the Winograd-transformed input V: 4x the activation — HBM is 288 GB).
+        # Always kept: recomputing it in the weight gradient, as round 1 did, measured 169.0 against 171.0 images/s.
+        saved = None
+        if wants_wgrad:
+            nsv = int(_native.lib().vcg_conv_saved_floats(cd))
             if nsv:
-                saved = torch.empty(nsv, dtype=torch.float32, device=dev)
-        if spec.norm:
-            # the conv and the statistics of the InstanceNorm that follows it in one call: the partial sums come out of
-            # the conv's own epilogue where its launch plan allows (csrc/conv_igemm.hip, vcg_conv_fwd_in)
-            c = spec.cout_pitch
-            mean = torch.empty((n, c), dtype=torch.float32, device=dev)
-            rstd = torch.empty((n, c), dtype=torch.float32, device=dev)
-            with _timed("conv_fwd", flops, tag):
-                ws = workspace(lib.vcg_conv_fwd_in_workspace(cd), dev)
-                if lazy is not None:
-                    _native.check(lib.vcg_conv_fwd_in_pre(_ptr(lazy[0]), _ptr(lazy[1]), _ptr(lazy[2]), lazy[3], _ptr(wf), _ptr(bias),
-                                                          _ptr(t), _ptr(mean), _ptr(rstd), IN_EPS, _ptr(saved), cd, _ptr(ws),
-                                                          ws.numel() * 4, _stream()), "vcg_conv_fwd_in_pre")
-                else:
-                    _native.check(lib.vcg_conv_fwd_in_h(_ptr(xp), _ptr(wf), _ptr(bias), _ptr(t), _ptr(mean), _ptr(rstd), IN_EPS,
-                                                        _ptr(saved), cd, _ptr(ws), ws.numel() * 4, x_amax, _stream()), "vcg_conv_fwd_in")
-            resp = as_phys(residual) if residual is not None else None
-            if spec.shuffle:
-                outp = torch.empty((n, 2 * ho, 2 * wo, c // 4), dtype=torch.float32, device=dev)
-                cout_log = spec.cout // 4
-            else:
-                outp = torch.empty((n, ho, wo, c), dtype=torch.float32, device=dev)
-                cout_log = spec.cout
-            if defer and (residual is not None or spec.shuffle):
-                raise RuntimeError("a block with a residual or a shuffled store cannot defer its InstanceNorm")
-            if not defer:
-                with _timed("in_fwd"):
-                    _native.check(lib.vcg_in_apply_h(_ptr(t), _ptr(mean), _ptr(rstd), _ptr(resp), _ptr(outp), n, ho, wo, c,
-                                                     spec.post_act, int(spec.shuffle), ctypes.byref(out_amax), _stream()), "vcg_in_apply")
-        else:
-            if residual is not None or spec.shuffle or spec.post_act:
-                raise RuntimeError("residual/shuffle/post_act need norm=True")
-            with _timed("conv_fwd", flops, tag):
-                ws = workspace(lib.vcg_conv_fwd_workspace(cd), dev)
-                if lazy is not None:
-                    _native.check(lib.vcg_conv_fwd_in_pre(_ptr(lazy[0]), _ptr(lazy[1]), _ptr(lazy[2]), lazy[3], _ptr(wf), _ptr(bias),
-                                                          _ptr(t), None, None, IN_EPS, _ptr(saved), cd, _ptr(ws), ws.numel() * 4,
-                                                          _stream()), "vcg_conv_fwd_in_pre")
-                else:
-                    _native.check(lib.vcg_conv_fwd_in_h(_ptr(xp), _ptr(wf), _ptr(bias), _ptr(t), None, None, IN_EPS, _ptr(saved), cd,
-                                                        _ptr(ws), ws.numel() * 4, x_amax, _stream()), "vcg_conv_fwd_in")
+                saved = torch.empty(nsv, dtype=torch.float32, device=x.device)
+        t, mean, rstd = conv_forward(spec, cd, wf, bias, xp, x_amax, lazy, spec.norm, saved, flops, tag)
+        out_amax = 0
+        if not spec.norm:
             outp, cout_log = t, spec.cout
-        ctx.spec, ctx.cd, ctx.dims, ctx.flops, ctx.tag = spec, cd, (n, h, w, ho, wo), flops, tag
+        elif defer:
+            outp, cout_log = norm_out(t, spec.cout)      # allocated, not written
+        else:
+            resp = as_phys(residual) if residual is not None else None
+            outp, cout_log, out_amax = norm_apply(t, mean, rstd, spec.post_act, spec.cout, resp, spec.shuffle)
+        ctx.spec, ctx.cd, ctx.flops, ctx.tag = spec, cd, flops, tag
         ctx.wparam, ctx.bparam = wparam, bparam
         ctx.has_res = residual is not None
         ctx.saved_state = saved
@@ -627,51 +713,29 @@ class _ConvBlockFn(torch.autograd.Function):
         if defer and spec.norm:
             # the storage of `out` stays unwritten: its consumer normalises t in its own gather, or fills it (materialize)
             out._vcg_lazy = (t, mean, rstd, spec.post_act, out._version, out.data_ptr())
-        elif AMAX_HANDLES:
-            _amax_tag(out, out_amax.value)    # for the block that consumes this very tensor object
+        else:
+            _amax_tag(out, out_amax)          # for the block that consumes this very tensor object
         return out
 
     @staticmethod
     def backward(ctx, g):
         lib = _native.lib()
         spec, cd = ctx.spec, ctx.cd
-        n, h, w, ho, wo = ctx.dims
         xp, t, mean, rstd, wf = ctx.saved_tensors
         dev = t.device
         gp = as_phys(g)
         d_res = g if ctx.has_res else None
-        c = spec.cout_pitch
         wparam, bparam = ctx.wparam, ctx.bparam
         want_w = wparam is not None and wparam.requires_grad and id(wparam) not in _NO_WGRAD
-        # conv -> act -> InstanceNorm (D, U, R.conv1): the bias gradient is the column sum of dt, taken by the pass that writes dt
-        # (include/vcg.h, vcg_in_bwd_bias) instead of a pass of its own inside the weight gradient.  VCG_BIAS_IN_BWD=0: as before.
-        gb_here = None
-        if spec.norm and spec.epi_act != ACT_NONE and want_w and BIAS_IN_BWD and bparam is not None and bparam.requires_grad:
-            gb_here = _grad_buffer(bparam)
-        if spec.norm:
-            dt = torch.empty_like(t)
-            wsb = lib.vcg_in_workspace(n, ho * wo, c)
-            ws = workspace(wsb, dev)
-            with _timed("in_bwd"):
-                h = ctypes.c_uint64(0)
-                if gb_here is not None:
-                    _native.check(lib.vcg_in_bwd_bias(_ptr(gp), _ptr(t), _ptr(mean), _ptr(rstd), _ptr(dt), n, ho, wo, c,
-                                                      spec.epi_act, spec.post_act, int(spec.shuffle), _ptr(gb_here), spec.cout,
-                                                      _ptr(ws), ws.numel() * 4, ctypes.byref(h), _stream()), "vcg_in_bwd_bias")
-                else:
-                    _native.check(lib.vcg_in_bwd_h(_ptr(gp), _ptr(t), _ptr(mean), _ptr(rstd), _ptr(dt), n, ho, wo, c,
-                                                   spec.epi_act, spec.post_act, int(spec.shuffle), _ptr(ws), ws.numel() * 4,
-                                                   ctypes.byref(h), _stream()), "vcg_in_bwd")
-            dt_amax = h.value if AMAX_HANDLES else 0
-        elif spec.epi_act != ACT_NONE:
-            dt = torch.empty_like(t)
-            h = ctypes.c_uint64(0)
-            _native.check(lib.vcg_act_bwd_h(_ptr(gp), _ptr(t), _ptr(dt), t.numel(), spec.epi_act, ctypes.byref(h), _stream()), "vcg_act_bwd")
-            dt_amax = h.value if AMAX_HANDLES else 0
-        else:
-            dt = gp
+        want_b = want_w and bparam is not None and bparam.requires_grad
+        # conv -> act -> InstanceNorm (D, U, R.conv1): the bias gradient is the column sum of dt, taken by the pass that writes
+        # dt instead of a pass of its own inside the weight gradient (same box, 4 runs: 36.49 / 36.47 against 36.48 / 36.49 ms
+        # per step — those column sums ran on the side stream —, -2 GB, -64 launches)
+        gb_here = _grad_buffer(bparam) if (want_b and spec.norm and spec.epi_act != ACT_NONE) else None
+        dt, dt_amax = block_dt(spec, gp, t, mean, rstd, gb_here)
+        if dt is gp:
             dt_amax = _amax_of(g)
-        if not dt_amax and AMAX_HANDLES:
+        if not dt_amax:
             dt_amax = _measured_amax(dt)      # on this stream, before the weight gradient forks off: both gradients take it
         saved = ctx.saved_state
         # x as the forward saw it?  (autograd refuses a saved tensor that was modified in place, so this only guards a
@@ -682,36 +746,29 @@ class _ConvBlockFn(torch.autograd.Function):
             # gradient (`no_wgrad`: the G phase through a discriminator), whose retained graph is differentiated again
             ctx.saved_state = None
             gw = _grad_buffer(wparam)
-            gb = _grad_buffer(bparam) if (bparam is not None and bparam.requires_grad) else None
+            gb = _grad_buffer(bparam) if want_b else None
             if spec.norm and spec.epi_act == ACT_NONE:
                 # InstanceNorm directly on conv + bias (CaSb, R.conv2): the mean subtraction cancels the bias, its gradient
                 # is identically zero (the reference's autograd returns rounding noise of ~1e-9 there: the column sums of
                 # a dt whose columns sum to zero) — the buffer stays at its zeros and the column-sum kernels are not run
                 gb = None
             if gb_here is not None:
-                gb = None            # already accumulated by vcg_in_bwd_bias above, on the main stream
+                gb = None            # already accumulated by block_dt above, on the main stream
             if ctx.x_deferred and saved is None:
                 raise RuntimeError("the weight gradient of a layer that took a deferred-InstanceNorm input needs the forward's kept "
-                                   "state (a second backward through the same graph, or VCG_KEEP_FORWARD_STATE=0 set after the forward)")
-            wsb = lib.vcg_conv_wgrad_workspace(cd)
-
-            def run_wgrad():
-                ws = workspace(wsb, dev)
-                with _timed("conv_wgrad", ctx.flops, ctx.tag):
-                    _native.check(lib.vcg_conv_wgrad_saved_h(_ptr(xp), _ptr(dt), _ptr(gw), _ptr(gb), _ptr(saved), cd, _ptr(ws),
-                                                             ws.numel() * 4, x_amax, dt_amax, _stream()), "vcg_conv_wgrad")
+                                   "state (a second backward through the same graph)")
             if _OVERLAP[0]:
                 side = _side_stream(dev)
                 side.wait_stream(torch.cuda.current_stream(dev))      # dt (and, the first time, x) are ready
                 with torch.cuda.stream(side):
-                    run_wgrad()
+                    conv_wgrad(cd, xp, dt, gw, gb, saved, x_amax, dt_amax, ctx.flops, ctx.tag)
                 xp.record_stream(side)                                # the allocator must not recycle them under the side stream
                 dt.record_stream(side)
                 if saved is not None:
                     saved.record_stream(side)
                 wstream = side
             else:
-                run_wgrad()
+                conv_wgrad(cd, xp, dt, gw, gb, saved, x_amax, dt_amax, ctx.flops, ctx.tag)
                 wstream = torch.cuda.current_stream(dev)
             members = getattr(wparam, "_vcg_members", None)
             if members is not None:
@@ -735,12 +792,7 @@ class _ConvBlockFn(torch.autograd.Function):
                     GRAD_READY_HOOK[0](wparam, bparam, wstream)
         dx = None
         if ctx.needs_input_grad[0] and id(spec) not in _NO_DGRAD:
-            dxp = torch.empty_like(xp)
-            with _timed("conv_dgrad", ctx.flops, ctx.tag):
-                ws = workspace(lib.vcg_conv_dgrad_workspace(cd), dev)
-                _native.check(lib.vcg_conv_dgrad_h(_ptr(dt), _ptr(wf), _ptr(dxp), cd, _ptr(ws), ws.numel() * 4, dt_amax,
-                                                   _stream()), "vcg_conv_dgrad")
-            dx = logical_of(dxp, spec.cin_phys_log)
+            dx = logical_of(conv_dgrad(cd, dt, wf, dt_amax, ctx.flops, ctx.tag), spec.cin_phys_log)
         return dx, None, None, d_res, None, None, None, None
 
 
@@ -752,8 +804,8 @@ def conv_block(x, weight, bias, spec, residual=None, defer=False):
 
 
 # ------------------------------------------------------------------ two convolutions of one input as one (VAE bottleneck: mu and logvar.0)
-# VCG_FUSE_MU_LOGVAR=0: two separate convolutions, as in round 3 (A/B measurements)
-FUSE_MU_LOGVAR = os.environ.get("VCG_FUSE_MU_LOGVAR", "1") != "0"
+# False (an A/B run or a test sets the attribute): two separate convolutions, as in round 3
+FUSE_MU_LOGVAR = True
 
 
 class FusedConvPair:
@@ -768,15 +820,11 @@ class FusedConvPair:
         self.w = self.bias = None
         self.key = None
         self.epoch = [0]
-        self._stream = self._event = None          # where / when the concatenated copy was last refreshed
+        self._written = _WrittenOn()               # where / when the concatenated copy was last refreshed
 
     def tensors(self):
         wa, wb, ba, bb = self.a.weight, self.b.weight, self.a.bias, self.b.bias
-
-        def k(t):
-            ep = getattr(t, "_vcg_epoch", None)
-            return (ep[0] if ep is not None else PARAM_EPOCH[0], id(ep), t._version, t.data_ptr())
-        key = (k(wa), k(wb), k(ba), k(bb), wa.device)
+        key = (_param_key(wa), _param_key(wb), _param_key(ba), _param_key(bb), wa.device)
         if self.w is None or self.w.device != wa.device:
             dev = wa.device
             self.w = torch.nn.Parameter(torch.empty((wa.shape[0] + wb.shape[0],) + tuple(wa.shape[1:]), dtype=torch.float32, device=dev))
@@ -796,13 +844,9 @@ class FusedConvPair:
                 self.bias.data[ca:].copy_(bb.data)
             self.epoch[0] += 1
             self.key = key
-            self._stream = torch.cuda.current_stream(wa.device)
-            self._event = torch.cuda.Event()
-            self._event.record(self._stream)
-        elif self._event is not None:
-            cur = torch.cuda.current_stream(wa.device)
-            if cur != self._stream:               # refreshed by the other direction's chain (DirectionFork): order after it
-                cur.wait_event(self._event)
+            self._written.mark(wa.device)
+        else:
+            self._written.order_reader(wa.device)      # refreshed by the other direction's chain (DirectionFork)
         rg = wa.requires_grad or wb.requires_grad
         self.w.requires_grad_(rg)
         self.bias.requires_grad_(rg)
