@@ -282,6 +282,29 @@ int vcg_grad_loss_fwd(const float* a, const float* b, float* out, int N, int H, 
    gradient with respect to b. */
 int vcg_grad_loss_bwd(const float* a, const float* b, const float* gout, float* ga, int N, int H, int W, int scales,
                       void* stream);
+/* Focal frequency loss (new: the reference has no spectral term; Jiang et al., ICCV 2021, at its defaults patch_factor 1 and no
+   ave_spectrum / log_matrix / batch_matrix).  With d = a - b and, for each of the 3 N planes (image n, logical channel c),
+     D = F_H d F_W,  F_n[j, k] = exp(-2 pi i j k / n) / sqrt(n)   (the orthonormal 2-D DFT),   p = |D|^2,
+     m = |D|^alpha  (alpha = 0: m = 1, also where D = 0),
+     w = m / max over the plane of m, 0 where that max is 0, clamped to [0, 1], a constant for the gradient:
+     out[0] = 1 / (3 N H W)  sum over planes and frequencies of  w p.
+   a (generated), b (target): (N, H, W, 4) fp32, the networks' layout, 16-byte aligned, channel 3 never read; H, W in
+   1 .. VCG_FREQ_MAX_SIDE independent (no power of two asked for: the DFT is two matrix products on the fp32 MFMA, the twiddles
+   looked up at (j k) mod n in a table of n entries built per call), N <= 21845; alpha finite and >= 0.  A NaN operand gives NaN.
+   spec: vcg_freq_loss_spectrum(N, H, W) bytes, 16-byte aligned: the state the forward keeps for the backward (the spectrum and
+   the plane maxima, layout private to the library).  ws: vcg_freq_loss_workspace(N, H, W) bytes of scratch, 16-byte aligned,
+   one size for both directions.  Both sizes are multiples of 16; 0 and vcg_last_error for bad sizes.  Partial sums go to slots
+   of their own and are added in a fixed order — no float atomics, the same input gives the same bits.  csrc/freq_loss.hip. */
+#define VCG_FREQ_MAX_SIDE 2048
+size_t vcg_freq_loss_workspace(int N, int H, int W);
+size_t vcg_freq_loss_spectrum(int N, int H, int W);
+int vcg_freq_loss_fwd(const float* a, const float* b, float* out, int N, int H, int W, float alpha, void* spec,
+                      size_t spec_bytes, void* ws, size_t ws_bytes, void* stream);
+/* ga = gout[0] * d loss / d a = gout[0] 2 / (3 N H W) Re(F_H^H (w . D) F_W^H), (N, H, W, 4) with channel 3 = 0, written for
+   every pixel; gout is read on the device.  Reads spec as the forward with the same N, H, W, alpha left it, not a and b.
+   There is no gradient with respect to b. */
+int vcg_freq_loss_bwd(const void* spec, size_t spec_bytes, const float* gout, float* ga, int N, int H, int W, float alpha,
+                      void* ws, size_t ws_bytes, void* stream);
 /* out[0] = sum_i w[i]*(*s[i]) ; the composite loss lines Networks.py:941,2012-2018 */
 int vcg_lincomb_fwd(const float* const* s, const float* w, int count, float* out, void* stream);
 

@@ -1,9 +1,11 @@
 """Atomic losses with the reference's class surface (Losses.py:14-121 of the reference),
 each reduction a HIP kernel (wavefront shuffle -> block partial -> ordered final sum).
 
-Only the six atomic classes (and StructuralLoss and GradientMatchingLoss, which the reference lacks) exist here: the reference's composite loss classes
+Only the six atomic classes (and StructuralLoss, GradientMatchingLoss and FocalFrequencyLoss, which the reference lacks) exist here: the reference's composite loss classes
 (Losses.py:123-379) are dead code there and are not part of the training step.
 """
+import math
+
 import torch.nn as nn
 
 from . import ops
@@ -51,6 +53,21 @@ class GradientMatchingLoss(nn.Module):
 
     def forward(self, generated, target):
         return ops.grad_match_loss(generated, target, self.scales)
+
+
+class FocalFrequencyLoss(nn.Module):
+    """Focal frequency loss (Jiang et al., ICCV 2021, patch_factor 1): the squared distance between the orthonormal 2-D spectra
+    of generated and target, each frequency weighted by |difference|^alpha over its plane's maximum, the weight a constant for
+    the gradient (new: the reference has no spectral term)."""
+
+    def __init__(self, alpha=1.0):
+        super().__init__()
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not math.isfinite(alpha) or alpha < 0:
+            raise ValueError(f"alpha must be a finite number >= 0, got {alpha!r}")
+        self.alpha = float(alpha)
+
+    def forward(self, generated, target):
+        return ops.freq_loss(generated, target, self.alpha)
 
 
 class GANLossGenerator(nn.Module):

@@ -19,7 +19,7 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .Losses import (CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, GradientMatchingLoss, IdentityLoss,
+from .Losses import (CycleConsistencyLoss, FocalFrequencyLoss, GANLossDiscriminator, GANLossGenerator, GradientMatchingLoss, IdentityLoss,
                      StructuralLoss, KLDivergenceLoss, TranslationLoss)
 from .image_pool import ImagePool, pool_seed as _pool_seed
 from .optim import FusedAdam
@@ -406,6 +406,15 @@ def _grad_matching(kwargs):
     return lam, (GradientMatchingLoss(kwargs.get("grad_scales", 4)) if lam > 0.0 else None)
 
 
+def _focal_frequency(kwargs):
+    """(lambda_freq, FocalFrequencyLoss(freq_alpha) or None) of a configure_loss call, as _structural and _grad_matching: with the
+    weight at its default 0 no loss object exists and the step computes, launches and reports exactly what it did before."""
+    lam = float(kwargs.get("lambda_freq", 0.0))
+    if lam < 0.0:
+        raise ValueError(f"lambda_freq must be >= 0, got {lam}")
+    return lam, (FocalFrequencyLoss(kwargs.get("freq_alpha", 1.0)) if lam > 0.0 else None)
+
+
 def _backward_and_step(loss, optimizer, reducer):
     """zero_grad -> backward -> [data-parallel gradient exchange, its buckets launched from inside the backward] -> step."""
     optimizer.zero_grad()
@@ -610,6 +619,8 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         self.lambda_ssim = 0.0
         self.loss_grad_fn = None
         self.lambda_grad = 0.0
+        self.loss_freq_fn = None
+        self.lambda_freq = 0.0
         self.apply(self._init_weights)
 
     def _init_weights(self, module):
@@ -626,6 +637,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         self.loss_fn = TranslationLoss()
         self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
         self.lambda_grad, self.loss_grad_fn = _grad_matching(kwargs)
+        self.lambda_freq, self.loss_freq_fn = _focal_frequency(kwargs)
 
     def _extra_terms(self, output, y):
         """The optional terms beside the L1, in the order they are reported: {name: device scalar} and their weights."""
@@ -636,6 +648,9 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         if getattr(self, "loss_grad_fn", None) is not None:
             extra["loss_grad"] = self.loss_grad_fn(output, y)
             weights.append(self.lambda_grad)
+        if getattr(self, "loss_freq_fn", None) is not None:
+            extra["loss_freq"] = self.loss_freq_fn(output, y)
+            weights.append(self.lambda_freq)
         return extra, weights
 
     def training_step(self, batch):
@@ -689,7 +704,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         with torch.no_grad():
             x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
             output = self(x)
-            if self.loss_ssim_fn is not None or self.loss_grad_fn is not None:
+            if self.loss_ssim_fn is not None or self.loss_grad_fn is not None or self.loss_freq_fn is not None:
                 loss_trans = self.loss_fn(output, y)
                 extra, weights = self._extra_terms(output, y)
                 t = {"G_loss": ops.weighted_sum([loss_trans, *extra.values()], [1.0, *weights]), "loss_trans": loss_trans, **extra}
@@ -714,9 +729,11 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self.loss_kl_fn = None
         self.loss_ssim_fn = None
         self.loss_grad_fn = None
+        self.loss_freq_fn = None
         self.lambda_kl = 0
         self.lambda_ssim = 0.0
         self.lambda_grad = 0.0
+        self.lambda_freq = 0.0
         self.apply(self._init_weights)
 
     def _init_weights(self, module):
@@ -745,6 +762,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
         self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
         self.lambda_grad, self.loss_grad_fn = _grad_matching(kwargs)
+        self.lambda_freq, self.loss_freq_fn = _focal_frequency(kwargs)
 
     def _check_configured(self):
         if self.optimizer is None:
@@ -755,7 +773,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             raise ValueError("KL divergence loss function has not been configured yet.")
 
     def _losses(self, batch):
-        """-> (G(x), the step's scalars in the order they are reported: G_loss, loss_trans, loss_kl, [loss_ssim], [loss_grad])"""
+        """-> (G(x), the step's scalars in the order they are reported: G_loss, loss_trans, loss_kl, [loss_ssim], [loss_grad], [loss_freq])"""
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         output, mu, logvar = self(x)
         loss_trans = self.loss_trans_fn(output, y)
@@ -770,6 +788,10 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             named["loss_grad"] = self.loss_grad_fn(output, y)
             terms.append(named["loss_grad"])
             weights.append(self.lambda_grad)
+        if self.loss_freq_fn is not None:
+            named["loss_freq"] = self.loss_freq_fn(output, y)
+            terms.append(named["loss_freq"])
+            weights.append(self.lambda_freq)
         named["G_loss"] = ops.weighted_sum(terms, weights)
         return output, named
 
@@ -916,6 +938,8 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         self.lambda_ssim = 0.0
         self.loss_grad = None
         self.lambda_grad = 0.0
+        self.loss_freq = None
+        self.lambda_freq = 0.0
         # data-parallel hook: set by parallel.attach(); called as reducer(phase, optimizer)
         self.grad_reducer = None
 
@@ -960,6 +984,7 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
         self.lambda_ssim, self.loss_ssim = _structural(kwargs)
         self.lambda_grad, self.loss_grad = _grad_matching(kwargs)
+        self.lambda_freq, self.loss_freq = _focal_frequency(kwargs)
 
     def _check_configured(self, need_opt=True):
         if (self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None
@@ -1025,6 +1050,10 @@ class CycleVAEGAN(_GanMixin, nn.Module):
             t["loss_grad"] = ops.weighted_sum([self.loss_grad(FGx, x), self.loss_grad(GFy, y)], [1.0, 1.0])
             terms.append(t["loss_grad"])
             weights.append(self.lambda_grad)
+        if self.loss_freq is not None:               # the focal frequency cycle term, on the same operands
+            t["loss_freq"] = ops.weighted_sum([self.loss_freq(FGx, x), self.loss_freq(GFy, y)], [1.0, 1.0])
+            terms.append(t["loss_freq"])
+            weights.append(self.lambda_freq)
         t["G_loss"] = ops.weighted_sum(terms, weights)
         # discriminator objective on the SAME discriminator outputs (reference :2038-2040)
         t["D_loss_x_real"], _ = ops.mse_const(DXx, 1.0)
@@ -1048,6 +1077,8 @@ class CycleVAEGAN(_GanMixin, nn.Module):
             keys += ("loss_ssim",)
         if self.loss_grad is not None:
             keys += ("loss_grad",)
+        if self.loss_freq is not None:
+            keys += ("loss_freq",)
         return (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + (() if training else _GX_FY)
 
     def _pooled_d_terms(self, t, Gx, Fy):

@@ -1207,6 +1207,58 @@ def grad_match_loss(generated, target, scales=4):
     return _GradLossFn.apply(generated, target, int(scales))
 
 
+class _FreqLossFn(torch.autograd.Function):
+    """Focal frequency loss of (generated, target) (csrc/freq_loss.hip); the gradient reaches `generated` only.  The forward keeps
+    the spectrum of generated - target and the plane maxima; the backward reads those, not the images."""
+
+    @staticmethod
+    def forward(ctx, a, b, alpha):
+        lib = _native.lib()
+        if a.shape != b.shape:
+            raise RuntimeError(f"freq_loss: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
+        if a.dim() != 4 or a.shape[1] != 3:
+            raise RuntimeError(f"freq_loss: expected (N, 3, H, W) images, got shape {tuple(a.shape)}")
+        ap, bp = as_phys(a), as_phys(b)
+        n, h, w, _ = ap.shape
+        out = torch.empty((), dtype=torch.float32, device=a.device)
+        need, keep = lib.vcg_freq_loss_workspace(n, h, w), lib.vcg_freq_loss_spectrum(n, h, w)
+        if need == 0 or keep == 0:
+            _native.check(-1, "vcg_freq_loss_workspace")
+        spec = torch.empty(keep // 4, dtype=torch.float32, device=a.device)
+        ws = workspace(need, a.device)
+        _native.check(lib.vcg_freq_loss_fwd(_ptr(ap), _ptr(bp), _ptr(out), n, h, w, alpha, _ptr(spec), keep, _ptr(ws),
+                                            ws.numel() * 4, _stream()), "vcg_freq_loss_fwd")
+        ctx.save_for_backward(spec)
+        ctx.geom = (n, h, w, alpha)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        lib = _native.lib()
+        spec, = ctx.saved_tensors
+        n, h, w, alpha = ctx.geom
+        g = g.contiguous()
+        ga = torch.empty((n, h, w, 4), dtype=torch.float32, device=spec.device)
+        ws = workspace(lib.vcg_freq_loss_workspace(n, h, w), spec.device)
+        _native.check(lib.vcg_freq_loss_bwd(_ptr(spec), spec.numel() * 4, _ptr(g), _ptr(ga), n, h, w, alpha, _ptr(ws),
+                                            ws.numel() * 4, _stream()), "vcg_freq_loss_bwd")
+        return logical_of(ga, 3), None, None
+
+
+def freq_loss(generated, target, alpha=1.0):
+    """Focal frequency loss (Jiang et al. 2021) of (N, 3, H, W) images, H, W in 1..2048: the mean over planes and frequencies of
+    w |D|^2, D the orthonormal 2-D DFT of generated - target and w = |D|^alpha over its plane maximum, a constant for the
+    gradient: a 0-dim fp32 tensor.  `target` is an input image: no gradient."""
+    alpha = float(alpha)
+    if not math.isfinite(alpha) or alpha < 0.0:
+        raise RuntimeError(f"freq_loss: alpha must be finite and >= 0, got {alpha!r}")
+    if target.requires_grad:
+        raise RuntimeError("freq_loss: the target must not require a gradient (only d loss / d generated is computed)")
+    return _FreqLossFn.apply(generated, target, alpha)
+
+
 class _MseConstFn(torch.autograd.Function):
     """nn.MSELoss()(d, full_like(d, target)) and d.mean(); Losses.py:80-81,99-100, Networks.py:2048-2051."""
 

@@ -42,6 +42,7 @@ REFERENCE_ARCHS = ["autoencoder", "doubleae", "doublevae", "vae", "aegan", "vaeg
                    "cycleaegan", "cyclevaegan"]
 BUILT = tuple(REFERENCE_ARCHS)
 SSIM_ARCHS = ("autoencoder", "vae", "cycleaegan", "cyclevaegan")     # the models whose configure_loss takes lambda_ssim
+FREQ_ARCHS = SSIM_ARCHS                # ... and lambda_freq / freq_alpha (the focal frequency term)
 GRAD_ARCHS = SSIM_ARCHS                # ... and lambda_grad / grad_scales: the term sits wherever the structural one does
 
 
@@ -207,6 +208,19 @@ def grad_weight(text):
     return value
 
 
+def _nonneg(flag, meaning):
+    """argparse type of --lambda_freq / --freq_alpha: a finite number >= 0."""
+    def parse(text):
+        try:
+            value = float(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+        if not math.isfinite(value) or value < 0.0:
+            raise argparse.ArgumentTypeError(f"{flag} must be finite and >= 0{meaning}, got {text}")
+        return value
+    return parse
+
+
 def ema_decay_value(text):
     """argparse type of --ema_decay: a finite decay in [0, 1) (0: off)."""
     try:
@@ -260,6 +274,11 @@ def build_parser():
                         "beside the L1 (" + ", ".join(GRAD_ARCHS) + "); 0: not computed")
     p.add_argument("--grad_scales", type=int, default=4, choices=(1, 2, 3, 4),
                    help="number of scales of the gradient-matching term; scale s keeps every 2^s-th pixel")
+    p.add_argument("--lambda_freq", type=_nonneg("--lambda_freq", " (0: the term is not computed)"), default=0.0,
+                   help="weight of the focal frequency term (the weighted squared distance between the 2-D spectra of generated "
+                        "and target) beside the L1 (" + ", ".join(FREQ_ARCHS) + "); 0: not computed")
+    p.add_argument("--freq_alpha", type=_nonneg("--freq_alpha", ""), default=1.0,
+                   help="exponent of the focal frequency term's spectrum weight |difference|^alpha; 0: an unweighted spectral MSE")
     p.add_argument("--clip_grad_norm", type=clip_bound, default=0.0,
                    help="clip each optimizer's gradient to this global 2-norm inside the fused Adam step (every architecture); "
                         "a step whose gradient holds a NaN / Inf is skipped; 0: off")
@@ -354,6 +373,15 @@ def main(args):
     grad_scales = getattr(args, "grad_scales", 4)
     if grad_scales not in (1, 2, 3, 4):
         raise ValueError(f"--grad_scales must be 1, 2, 3 or 4, got {grad_scales}")
+    lambda_freq = getattr(args, "lambda_freq", 0.0)
+    if not math.isfinite(lambda_freq) or lambda_freq < 0.0:
+        raise ValueError(f"--lambda_freq must be finite and >= 0 (0: the term is not computed), got {lambda_freq}")
+    if lambda_freq != 0.0 and args.architecture not in FREQ_ARCHS:
+        raise ValueError(f"--lambda_freq is supported by {', '.join(FREQ_ARCHS)} only, not by {args.architecture}: "
+                         "the flag would be ignored")
+    freq_alpha = getattr(args, "freq_alpha", 1.0)
+    if not math.isfinite(freq_alpha) or freq_alpha < 0.0:
+        raise ValueError(f"--freq_alpha must be finite and >= 0, got {freq_alpha}")
     clip = getattr(args, "clip_grad_norm", 0.0)
     if not math.isfinite(clip) or clip < 0.0:
         raise ValueError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {clip}")
@@ -422,7 +450,8 @@ def main(args):
         print(f"Averaged generator weights (decay {ema_decay}): the test loss, and with it best_model.pth, is the averaged weights'")
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
                          lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
-                         lambda_ssim=getattr(args, "lambda_ssim", 0.0), lambda_grad=lambda_grad, grad_scales=grad_scales)
+                         lambda_ssim=getattr(args, "lambda_ssim", 0.0), lambda_grad=lambda_grad, grad_scales=grad_scales,
+                         lambda_freq=lambda_freq, freq_alpha=freq_alpha)
     if world > 1:
         parallel.attach(model)
     same_xy = args.architecture in ("autoencoder", "vae")
