@@ -1,20 +1,11 @@
-"""CPU: the focal frequency loss's C ABI, binding and command line — everything about it that needs no GPU."""
+"""CPU: the focal frequency loss's C ABI and binding — what needs no GPU (flags, configure_loss: test_image_terms_host.py)."""
 import ctypes
-import importlib
 import os
 import re
 import subprocess
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("vcg_freq_loss_workspace", "vcg_freq_loss_spectrum", "vcg_freq_loss_fwd", "vcg_freq_loss_bwd")
-ARCHS = ("autoencoder", "vae", "cycleaegan", "cyclevaegan")
-
-
-@pytest.fixture(scope="module")
-def train(pkg):
-    return importlib.import_module("vae-cyclegan-implementation_amd.train")
 
 
 def side_cap():
@@ -107,68 +98,3 @@ def test_bad_arguments_are_rejected_without_touching_the_gpu(pkg):
         assert bwd(**{name: None}) != 0 and "null pointer" in err()
     assert bwd(ga=P(base + 8)) != 0 and "aligned" in err()
     assert bwd(gout=P(base + 128 + 1)) != 0 and "aligned" in err()
-
-
-def test_parser_defaults_and_refusals(train, capsys):
-    p = train.build_parser()
-    args = p.parse_args([])
-    assert args.lambda_freq == 0.0 and args.freq_alpha == 1.0
-    args = p.parse_args(["--lambda_freq", "0.5", "--freq_alpha", "0"])
-    assert args.lambda_freq == 0.5 and args.freq_alpha == 0.0
-    for flag in ("--lambda_freq", "--freq_alpha"):
-        for bad in ("-1", "nan", "inf", "x"):
-            with pytest.raises(SystemExit):
-                p.parse_args([flag, bad])
-            assert flag in capsys.readouterr().err
-
-
-@pytest.mark.parametrize("arch", ["doubleae", "doublevae", "aegan", "vaegan", "cycleae", "cyclevae"])
-def test_lambda_freq_is_refused_for_the_other_architectures_before_any_device_is_touched(train, arch):
-    args = train.build_parser().parse_args(["--architecture", arch, "--lambda_freq", "0.5"])
-    with pytest.raises(ValueError, match="lambda_freq") as e:
-        train.main(args)
-    for name in ARCHS:
-        assert name in str(e.value)
-    assert train.FREQ_ARCHS is train.SSIM_ARCHS                 # one list of models, shared
-
-
-def test_main_refuses_bad_values_of_an_args_object_built_without_the_parser(train):
-    args = train.build_parser().parse_args(["--architecture", "vae"])
-    args.lambda_freq = -1.0
-    with pytest.raises(ValueError, match="lambda_freq"):
-        train.main(args)
-    args.lambda_freq = float("nan")
-    with pytest.raises(ValueError, match="lambda_freq"):
-        train.main(args)
-    args.lambda_freq, args.freq_alpha = 0.5, -2.0
-    with pytest.raises(ValueError, match="freq_alpha"):
-        train.main(args)
-    args = train.build_parser().parse_args(["--architecture", "aegan"])
-    del args.freq_alpha
-    args.lambda_freq = 0.5
-    with pytest.raises(ValueError, match="lambda_freq"):
-        train.main(args)
-
-
-def test_loss_object_exists_only_for_a_positive_weight(pkg):
-    N = pkg.Networks
-    for make, attr in ((N.Autoencoder, "loss_freq_fn"), (lambda: N.VariationalAutoencoder(latent_dim=8), "loss_freq_fn"),
-                       (lambda: N.CycleAEGAN(paired=False), "loss_freq"), (lambda: N.CycleVAEGAN(latent_dim=8, paired=False), "loss_freq")):
-        m = make()
-        m.configure_loss()
-        assert getattr(m, attr) is None and m.lambda_freq == 0.0
-        m.configure_loss(lambda_freq=0.0, freq_alpha=0.5)
-        assert getattr(m, attr) is None
-        m.configure_loss(lambda_freq=0.5)
-        assert isinstance(getattr(m, attr), pkg.Losses.FocalFrequencyLoss) and m.lambda_freq == 0.5
-        assert getattr(m, attr).alpha == 1.0
-        m.configure_loss(lambda_freq=0.5, freq_alpha=0)
-        assert getattr(m, attr).alpha == 0.0
-        with pytest.raises(ValueError, match="lambda_freq"):
-            m.configure_loss(lambda_freq=-1.0)
-        with pytest.raises(ValueError, match="alpha"):
-            m.configure_loss(lambda_freq=0.5, freq_alpha=-1.0)
-    for bad in (-0.1, float("nan"), float("inf"), "1", True):
-        with pytest.raises(ValueError, match="alpha"):
-            pkg.Losses.FocalFrequencyLoss(bad)
-    assert "reference has no" in pkg.Losses.FocalFrequencyLoss.__doc__

@@ -1,4 +1,4 @@
-"""CPU: the structural loss's C ABI, binding and command line — everything about it that needs no GPU."""
+"""CPU: the structural loss's C ABI and binding — what needs no GPU (flags, configure_loss: test_image_terms_host.py)."""
 import ctypes
 import importlib
 import os
@@ -73,12 +73,6 @@ def test_bad_arguments_are_rejected_without_touching_the_gpu(pkg):
     assert lib.vcg_ssim_loss_bwd(a, b, gout, P(base + 256 + 4), 2, 32, 32, None) != 0 and "aligned" in err()
 
 
-def test_parser_has_lambda_ssim_defaulting_to_zero(train):
-    p = train.build_parser()
-    assert p.parse_args([]).lambda_ssim == 0.0
-    assert p.parse_args(["--lambda_ssim", "0.5"]).lambda_ssim == 0.5
-
-
 @pytest.mark.parametrize("arch", ["doubleae", "doublevae", "aegan", "vaegan", "cycleae", "cyclevae"])
 def test_lambda_ssim_is_refused_for_the_other_architectures_before_any_device_is_touched(train, arch):
     args = train.build_parser().parse_args(["--architecture", arch, "--lambda_ssim", "0.5"])
@@ -86,16 +80,3 @@ def test_lambda_ssim_is_refused_for_the_other_architectures_before_any_device_is
         train.main(args)
     for name in ("autoencoder", "vae", "cycleaegan", "cyclevaegan"):
         assert name in str(e.value)
-
-
-def test_structural_loss_object_exists_only_for_a_positive_weight(pkg):
-    N = pkg.Networks
-    m = N.Autoencoder()
-    m.configure_loss()
-    assert m.loss_ssim_fn is None and m.lambda_ssim == 0.0
-    m.configure_loss(lambda_ssim=0.0)
-    assert m.loss_ssim_fn is None
-    m.configure_loss(lambda_ssim=0.5)
-    assert isinstance(m.loss_ssim_fn, pkg.Losses.StructuralLoss) and m.lambda_ssim == 0.5
-    with pytest.raises(ValueError):
-        m.configure_loss(lambda_ssim=-1.0)

@@ -4,7 +4,7 @@ the headline model's two optimizers (CycleVAEGAN, latent 64: F + G and DX + DY),
 (4 B per parameter for the norm, 28 B for Adam).
 
 A kernel time is the median over 15 repetitions of (HIP-event time of 20 back-to-back calls) / 20 after 3 warm-up repetitions:
-what one more call costs a stream that is already busy, which is how the step sees it (tools/ssim_loss_bench.py's method).  The
+what one more call costs a stream that is already busy, which is how the step sees it (tools/image_loss_bench.py's method).  The
 norm is two launches (chunks, final sum).  Writes OUT/grad_clip_bench.txt (OUT defaults to profiles_out) and prints the same.
 
     python tools/grad_clip_bench.py

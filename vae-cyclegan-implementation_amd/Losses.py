@@ -5,6 +5,7 @@ Only the six atomic classes (and StructuralLoss, GradientMatchingLoss and FocalF
 (Losses.py:123-379) are dead code there and are not part of the training step.
 """
 import math
+from typing import NamedTuple
 
 import torch.nn as nn
 
@@ -68,6 +69,23 @@ class FocalFrequencyLoss(nn.Module):
 
     def forward(self, generated, target):
         return ops.freq_loss(generated, target, self.alpha)
+
+
+class ImageTerm(NamedTuple):
+    """One optional reconstruction term beside the L1: weighted by `lambda_<key>` (configure_loss keyword; `--lambda_<key>` in
+    train.py), reported as `loss_<key>`.  `option` is the keyword of its loss class's one constructor argument, if it has one."""
+    key: str
+    loss: type
+    option: str = None
+    default: object = None
+
+
+# the order of the rows is the order in which the steps report the terms
+IMAGE_TERMS = (
+    ImageTerm("ssim", StructuralLoss),
+    ImageTerm("grad", GradientMatchingLoss, "grad_scales", 4),
+    ImageTerm("freq", FocalFrequencyLoss, "freq_alpha", 1.0),
+)
 
 
 class GANLossGenerator(nn.Module):

@@ -19,8 +19,8 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .Losses import (CycleConsistencyLoss, FocalFrequencyLoss, GANLossDiscriminator, GANLossGenerator, GradientMatchingLoss, IdentityLoss,
-                     StructuralLoss, KLDivergenceLoss, TranslationLoss)
+from .Losses import (IMAGE_TERMS, CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss, KLDivergenceLoss,
+                     TranslationLoss)
 from .image_pool import ImagePool, pool_seed as _pool_seed
 from .optim import FusedAdam
 
@@ -388,31 +388,30 @@ def _clip_scalars(**optimizers):
     return out
 
 
-def _structural(kwargs):
-    """(lambda_ssim, StructuralLoss() or None) of a configure_loss call: with the weight at its default 0 no loss object exists and
-    the step computes, launches and reports exactly what it did before the term was added."""
-    lam = float(kwargs.get("lambda_ssim", 0.0))
-    if lam < 0.0:
-        raise ValueError(f"lambda_ssim must be >= 0, got {lam}")
-    return lam, (StructuralLoss() if lam > 0.0 else None)
+def _image_terms(kwargs):
+    """The optional image terms a configure_loss call switches on: ((reported name, weight, loss module), ...) for the rows of
+    Losses.IMAGE_TERMS whose lambda_<key> is > 0, in the table's order.  With a weight at its default 0 no loss object exists (the
+    term's option is then not looked at) and the step computes, launches and reports exactly what it did before the term was added."""
+    active = []
+    for row in IMAGE_TERMS:
+        lam = float(kwargs.get(f"lambda_{row.key}", 0.0))
+        if lam < 0.0:
+            raise ValueError(f"lambda_{row.key} must be >= 0, got {lam}")
+        if lam > 0.0:
+            option = () if row.option is None else (kwargs.get(row.option, row.default),)
+            active.append((f"loss_{row.key}", lam, row.loss(*option)))
+    return tuple(active)
 
 
-def _grad_matching(kwargs):
-    """(lambda_grad, GradientMatchingLoss(grad_scales) or None) of a configure_loss call, as _structural: with the weight at its
-    default 0 no loss object exists and the step computes, launches and reports exactly what it did before the term was added."""
-    lam = float(kwargs.get("lambda_grad", 0.0))
-    if lam < 0.0:
-        raise ValueError(f"lambda_grad must be >= 0, got {lam}")
-    return lam, (GradientMatchingLoss(kwargs.get("grad_scales", 4)) if lam > 0.0 else None)
-
-
-def _focal_frequency(kwargs):
-    """(lambda_freq, FocalFrequencyLoss(freq_alpha) or None) of a configure_loss call, as _structural and _grad_matching: with the
-    weight at its default 0 no loss object exists and the step computes, launches and reports exactly what it did before."""
-    lam = float(kwargs.get("lambda_freq", 0.0))
-    if lam < 0.0:
-        raise ValueError(f"lambda_freq must be >= 0, got {lam}")
-    return lam, (FocalFrequencyLoss(kwargs.get("freq_alpha", 1.0)) if lam > 0.0 else None)
+def _eval_image_terms(terms, pairs):
+    """The active terms (_image_terms) on the (generated, target) pairs, in the order they are reported: {name: device scalar} and
+    their weights.  One pair: the loss module's own output; two (the cycle models): their sum."""
+    named, weights = {}, []
+    for name, lam, fn in terms:
+        values = [fn(generated, target) for generated, target in pairs]
+        named[name] = values[0] if len(values) == 1 else ops.weighted_sum(values, [1.0] * len(values))
+        weights.append(lam)
+    return named, weights
 
 
 def _backward_and_step(loss, optimizer, reducer):
@@ -615,12 +614,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         self.optimizer = None
         self.grad_reducer = None
         self.loss_fn = None
-        self.loss_ssim_fn = None
-        self.lambda_ssim = 0.0
-        self.loss_grad_fn = None
-        self.lambda_grad = 0.0
-        self.loss_freq_fn = None
-        self.lambda_freq = 0.0
+        self.image_terms = ()
         self.apply(self._init_weights)
 
     def _init_weights(self, module):
@@ -635,23 +629,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
 
     def configure_loss(self, **kwargs):
         self.loss_fn = TranslationLoss()
-        self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
-        self.lambda_grad, self.loss_grad_fn = _grad_matching(kwargs)
-        self.lambda_freq, self.loss_freq_fn = _focal_frequency(kwargs)
-
-    def _extra_terms(self, output, y):
-        """The optional terms beside the L1, in the order they are reported: {name: device scalar} and their weights."""
-        extra, weights = {}, []
-        if getattr(self, "loss_ssim_fn", None) is not None:     # (a caller's stand-in for `self` need not know the terms)
-            extra["loss_ssim"] = self.loss_ssim_fn(output, y)
-            weights.append(self.lambda_ssim)
-        if getattr(self, "loss_grad_fn", None) is not None:
-            extra["loss_grad"] = self.loss_grad_fn(output, y)
-            weights.append(self.lambda_grad)
-        if getattr(self, "loss_freq_fn", None) is not None:
-            extra["loss_freq"] = self.loss_freq_fn(output, y)
-            weights.append(self.lambda_freq)
-        return extra, weights
+        self.image_terms = _image_terms(kwargs)
 
     def training_step(self, batch):
         """Written out (no _report): the reference's NaN / Inf guard reads the loss on the host before the update, and the plain
@@ -665,7 +643,8 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         output = self(x)
         loss_trans = self.loss_fn(output, y)
         G_loss = loss_trans
-        extra, weights = Autoencoder._extra_terms(self, output, y)
+        # (a caller's stand-in for `self` need not know the terms)
+        extra, weights = _eval_image_terms(getattr(self, "image_terms", ()), [(output, y)])
         if extra:
             G_loss = ops.weighted_sum([loss_trans, *extra.values()], [1.0, *weights])
         value = float(G_loss.detach())                 # the reference's isnan/isinf guard syncs here too (:357)
@@ -704,9 +683,9 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         with torch.no_grad():
             x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
             output = self(x)
-            if self.loss_ssim_fn is not None or self.loss_grad_fn is not None or self.loss_freq_fn is not None:
+            if self.image_terms:
                 loss_trans = self.loss_fn(output, y)
-                extra, weights = self._extra_terms(output, y)
+                extra, weights = _eval_image_terms(self.image_terms, [(output, y)])
                 t = {"G_loss": ops.weighted_sum([loss_trans, *extra.values()], [1.0, *weights]), "loss_trans": loss_trans, **extra}
                 return _report(self, t, (("G_loss", "G_loss"), ("total_loss", "G_loss")) + _same("loss_trans", *extra) + _GX,
                                False, Gx=output)
@@ -727,13 +706,8 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self.grad_reducer = None
         self.loss_trans_fn = None
         self.loss_kl_fn = None
-        self.loss_ssim_fn = None
-        self.loss_grad_fn = None
-        self.loss_freq_fn = None
         self.lambda_kl = 0
-        self.lambda_ssim = 0.0
-        self.lambda_grad = 0.0
-        self.lambda_freq = 0.0
+        self.image_terms = ()
         self.apply(self._init_weights)
 
     def _init_weights(self, module):
@@ -760,9 +734,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         self.loss_trans_fn = TranslationLoss()
         self.loss_kl_fn = KLDivergenceLoss()
         self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
-        self.lambda_ssim, self.loss_ssim_fn = _structural(kwargs)
-        self.lambda_grad, self.loss_grad_fn = _grad_matching(kwargs)
-        self.lambda_freq, self.loss_freq_fn = _focal_frequency(kwargs)
+        self.image_terms = _image_terms(kwargs)
 
     def _check_configured(self):
         if self.optimizer is None:
@@ -778,21 +750,9 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         output, mu, logvar = self(x)
         loss_trans = self.loss_trans_fn(output, y)
         loss_kl = self.loss_kl_fn(mu, logvar)
-        named = {"G_loss": None, "loss_trans": loss_trans, "loss_kl": loss_kl}
-        terms, weights = [loss_trans, loss_kl], [1.0, self.lambda_kl]
-        if self.loss_ssim_fn is not None:
-            named["loss_ssim"] = self.loss_ssim_fn(output, y)
-            terms.append(named["loss_ssim"])
-            weights.append(self.lambda_ssim)
-        if self.loss_grad_fn is not None:
-            named["loss_grad"] = self.loss_grad_fn(output, y)
-            terms.append(named["loss_grad"])
-            weights.append(self.lambda_grad)
-        if self.loss_freq_fn is not None:
-            named["loss_freq"] = self.loss_freq_fn(output, y)
-            terms.append(named["loss_freq"])
-            weights.append(self.lambda_freq)
-        named["G_loss"] = ops.weighted_sum(terms, weights)
+        extra, weights = _eval_image_terms(self.image_terms, [(output, y)])
+        named = {"G_loss": None, "loss_trans": loss_trans, "loss_kl": loss_kl, **extra}
+        named["G_loss"] = ops.weighted_sum([loss_trans, loss_kl, *extra.values()], [1.0, self.lambda_kl, *weights])
         return output, named
 
     def training_step(self, batch):
@@ -934,12 +894,7 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         self.loss_gan_disc = None
         self.loss_identity = None
         self.loss_kl = None
-        self.loss_ssim = None
-        self.lambda_ssim = 0.0
-        self.loss_grad = None
-        self.lambda_grad = 0.0
-        self.loss_freq = None
-        self.lambda_freq = 0.0
+        self.image_terms = ()
         # data-parallel hook: set by parallel.attach(); called as reducer(phase, optimizer)
         self.grad_reducer = None
 
@@ -982,9 +937,7 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         self.lambda_gan = kwargs.get("lambda_gan", 1.0)
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
-        self.lambda_ssim, self.loss_ssim = _structural(kwargs)
-        self.lambda_grad, self.loss_grad = _grad_matching(kwargs)
-        self.lambda_freq, self.loss_freq = _focal_frequency(kwargs)
+        self.image_terms = _image_terms(kwargs)
 
     def _check_configured(self, need_opt=True):
         if (self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None
@@ -1042,19 +995,10 @@ class CycleVAEGAN(_GanMixin, nn.Module):
             t["loss_identity"] = self.loss_identity(x, y, Fx, Gy)
             terms.append(t["loss_identity"])
             weights.append(self.lambda_identity)
-        if self.loss_ssim is not None:               # the structural cycle term; FGx and GFy are joined by now, as for loss_cycle
-            t["loss_ssim"] = ops.weighted_sum([self.loss_ssim(FGx, x), self.loss_ssim(GFy, y)], [1.0, 1.0])
-            terms.append(t["loss_ssim"])
-            weights.append(self.lambda_ssim)
-        if self.loss_grad is not None:               # the gradient-matching cycle term, on the structural term's operands
-            t["loss_grad"] = ops.weighted_sum([self.loss_grad(FGx, x), self.loss_grad(GFy, y)], [1.0, 1.0])
-            terms.append(t["loss_grad"])
-            weights.append(self.lambda_grad)
-        if self.loss_freq is not None:               # the focal frequency cycle term, on the same operands
-            t["loss_freq"] = ops.weighted_sum([self.loss_freq(FGx, x), self.loss_freq(GFy, y)], [1.0, 1.0])
-            terms.append(t["loss_freq"])
-            weights.append(self.lambda_freq)
-        t["G_loss"] = ops.weighted_sum(terms, weights)
+        # the optional cycle terms, each on the L1 cycle term's operands; FGx and GFy are joined by now, as for loss_cycle
+        extra, extra_weights = _eval_image_terms(self.image_terms, [(FGx, x), (GFy, y)])
+        t.update(extra)
+        t["G_loss"] = ops.weighted_sum(terms + list(extra.values()), weights + extra_weights)
         # discriminator objective on the SAME discriminator outputs (reference :2038-2040)
         t["D_loss_x_real"], _ = ops.mse_const(DXx, 1.0)
         t["D_loss_x_fake"], _ = ops.mse_const(DXFy, 0.0)
@@ -1073,12 +1017,7 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         keys = self._METRIC_KEYS + (self._MEAN_KEYS if training else ())
         if self.paired:
             keys += ("loss_identity",)
-        if self.loss_ssim is not None:
-            keys += ("loss_ssim",)
-        if self.loss_grad is not None:
-            keys += ("loss_grad",)
-        if self.loss_freq is not None:
-            keys += ("loss_freq",)
+        keys += tuple(name for name, _, _ in self.image_terms)
         return (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + (() if training else _GX_FY)
 
     def _pooled_d_terms(self, t, Gx, Fy):

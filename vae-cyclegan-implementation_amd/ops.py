@@ -1118,83 +1118,120 @@ def l1_loss(a, b):
     return _L1Fn.apply(a, b)
 
 
-class _SsimLossFn(torch.autograd.Function):
-    """1 - mean SSIM(generated, target) (csrc/ssim_loss.hip); the gradient reaches `generated` only."""
+def _call(entry, *args):
+    """lib.<entry>(*args), the entry looked up when it is called, its status checked."""
+    _native.check(getattr(_native.lib(), entry)(*args), entry)
+
+
+def _scratch(entry, *args):
+    """The byte count lib.<entry>(*args) asks for; 0 means the library refused the arguments."""
+    need = getattr(_native.lib(), entry)(*args)
+    if need == 0:
+        _native.check(-1, entry)
+    return need
+
+
+# The optional image losses differ in their library calls, their one option `opt` and what the backward reads; _ImageLossFn holds
+# everything else.  scratch(n, h, w, opt) -> workspace bytes; fwd(ap, bp, out, dims, opt, ws) -> the tensors kept for the backward;
+# bwd(kept, g, ga, dims, opt).
+class _SsimTerm:
+    """1 - mean SSIM(generated, target) (csrc/ssim_loss.hip)."""
+    name = "ssim_loss"
 
     @staticmethod
-    def forward(ctx, a, b):
-        lib = _native.lib()
+    def scratch(n, h, w, _):
+        return _scratch("vcg_ssim_loss_workspace", n, h, w)
+
+    @staticmethod
+    def fwd(ap, bp, out, dims, _, ws):
+        _call("vcg_ssim_loss_fwd", _ptr(ap), _ptr(bp), _ptr(out), *dims, _ptr(ws), ws.numel() * 4, _stream())
+        return ap, bp                             # the backward recomputes its coefficients from the two images
+
+    @staticmethod
+    def bwd(kept, g, ga, dims, _):
+        ap, bp = kept
+        _call("vcg_ssim_loss_bwd", _ptr(ap), _ptr(bp), _ptr(g), _ptr(ga), *dims, _stream())
+
+
+class _GradTerm:
+    """Multi-scale gradient-matching loss of (generated, target) (csrc/grad_loss.hip); opt: the number of scales."""
+    name = "grad_match_loss"
+
+    @staticmethod
+    def scratch(n, h, w, scales):
+        return _scratch("vcg_grad_loss_workspace", n, h, w, scales)
+
+    @staticmethod
+    def fwd(ap, bp, out, dims, scales, ws):
+        _call("vcg_grad_loss_fwd", _ptr(ap), _ptr(bp), _ptr(out), *dims, scales, _ptr(ws), ws.numel() * 4, _stream())
+        return ap, bp                             # the backward takes its signs from the two images
+
+    @staticmethod
+    def bwd(kept, g, ga, dims, scales):
+        ap, bp = kept
+        _call("vcg_grad_loss_bwd", _ptr(ap), _ptr(bp), _ptr(g), _ptr(ga), *dims, scales, _stream())
+
+
+class _FreqTerm:
+    """Focal frequency loss of (generated, target) (csrc/freq_loss.hip); opt: alpha.  The forward keeps the spectrum of
+    generated - target and the plane maxima; the backward reads those, not the images."""
+    name = "freq_loss"
+
+    @staticmethod
+    def scratch(n, h, w, _):
+        return _scratch("vcg_freq_loss_workspace", n, h, w)
+
+    @staticmethod
+    def fwd(ap, bp, out, dims, alpha, ws):
+        keep = _scratch("vcg_freq_loss_spectrum", *dims)
+        spec = torch.empty(keep // 4, dtype=torch.float32, device=ap.device)
+        _call("vcg_freq_loss_fwd", _ptr(ap), _ptr(bp), _ptr(out), *dims, alpha, _ptr(spec), keep, _ptr(ws), ws.numel() * 4, _stream())
+        return (spec,)
+
+    @staticmethod
+    def bwd(kept, g, ga, dims, alpha):
+        spec, = kept
+        ws = workspace(_FreqTerm.scratch(*dims, alpha), spec.device)
+        _call("vcg_freq_loss_bwd", _ptr(spec), spec.numel() * 4, _ptr(g), _ptr(ga), *dims, alpha, _ptr(ws), ws.numel() * 4, _stream())
+
+
+class _ImageLossFn(torch.autograd.Function):
+    """The loss `term` (_SsimTerm, _GradTerm, _FreqTerm) of (generated, target); the gradient reaches `generated` only."""
+
+    @staticmethod
+    def forward(ctx, term, a, b, opt):
         if a.shape != b.shape:
-            raise RuntimeError(f"ssim_loss: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
+            raise RuntimeError(f"{term.name}: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
         if a.dim() != 4 or a.shape[1] != 3:
-            raise RuntimeError(f"ssim_loss: expected (N, 3, H, W) images, got shape {tuple(a.shape)}")
+            raise RuntimeError(f"{term.name}: expected (N, 3, H, W) images, got shape {tuple(a.shape)}")
         ap, bp = as_phys(a), as_phys(b)
-        n, h, w, _ = ap.shape
+        dims = tuple(ap.shape[:3])
         out = torch.empty((), dtype=torch.float32, device=a.device)
-        need = lib.vcg_ssim_loss_workspace(n, h, w)
-        if need == 0:
-            _native.check(-1, "vcg_ssim_loss_workspace")
-        ws = workspace(need, a.device)
-        _native.check(lib.vcg_ssim_loss_fwd(_ptr(ap), _ptr(bp), _ptr(out), n, h, w, _ptr(ws), ws.numel() * 4, _stream()),
-                      "vcg_ssim_loss_fwd")
-        ctx.save_for_backward(ap, bp)             # the backward recomputes its coefficients from the two images
+        ws = workspace(term.scratch(*dims, opt), a.device)
+        ctx.save_for_backward(*term.fwd(ap, bp, out, dims, opt, ws))
+        ctx.call = (term, dims, opt)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None
-        lib = _native.lib()
-        ap, bp = ctx.saved_tensors
-        n, h, w, _ = ap.shape
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        term, dims, opt = ctx.call
         g = g.contiguous()
-        ga = torch.empty_like(ap)
-        _native.check(lib.vcg_ssim_loss_bwd(_ptr(ap), _ptr(bp), _ptr(g), _ptr(ga), n, h, w, _stream()), "vcg_ssim_loss_bwd")
-        return logical_of(ga, 3), None
+        ga = torch.empty((*dims, 4), dtype=torch.float32, device=g.device)
+        term.bwd(ctx.saved_tensors, g, ga, dims, opt)
+        return None, logical_of(ga, 3), None, None
+
+
+def _image_loss(term, generated, target, opt=None):
+    if target.requires_grad:
+        raise RuntimeError(f"{term.name}: the target must not require a gradient (only d loss / d generated is computed)")
+    return _ImageLossFn.apply(term, generated, target, opt)
 
 
 def ssim_loss(generated, target):
     """1 - mean SSIM over (N, 3, H, W) images, H, W >= 11: a 0-dim fp32 tensor.  `target` is an input image: no gradient."""
-    if target.requires_grad:
-        raise RuntimeError("ssim_loss: the target must not require a gradient (only d loss / d generated is computed)")
-    return _SsimLossFn.apply(generated, target)
-
-
-class _GradLossFn(torch.autograd.Function):
-    """Multi-scale gradient-matching loss of (generated, target) (csrc/grad_loss.hip); the gradient reaches `generated` only."""
-
-    @staticmethod
-    def forward(ctx, a, b, scales):
-        lib = _native.lib()
-        if a.shape != b.shape:
-            raise RuntimeError(f"grad_match_loss: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
-        if a.dim() != 4 or a.shape[1] != 3:
-            raise RuntimeError(f"grad_match_loss: expected (N, 3, H, W) images, got shape {tuple(a.shape)}")
-        ap, bp = as_phys(a), as_phys(b)
-        n, h, w, _ = ap.shape
-        out = torch.empty((), dtype=torch.float32, device=a.device)
-        need = lib.vcg_grad_loss_workspace(n, h, w, scales)
-        if need == 0:
-            _native.check(-1, "vcg_grad_loss_workspace")
-        ws = workspace(need, a.device)
-        _native.check(lib.vcg_grad_loss_fwd(_ptr(ap), _ptr(bp), _ptr(out), n, h, w, scales, _ptr(ws), ws.numel() * 4, _stream()),
-                      "vcg_grad_loss_fwd")
-        ctx.save_for_backward(ap, bp)             # the backward takes its signs from the two images
-        ctx.scales = scales
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None
-        lib = _native.lib()
-        ap, bp = ctx.saved_tensors
-        n, h, w, _ = ap.shape
-        g = g.contiguous()
-        ga = torch.empty_like(ap)
-        _native.check(lib.vcg_grad_loss_bwd(_ptr(ap), _ptr(bp), _ptr(g), _ptr(ga), n, h, w, ctx.scales, _stream()),
-                      "vcg_grad_loss_bwd")
-        return logical_of(ga, 3), None, None
+    return _image_loss(_SsimTerm, generated, target)
 
 
 def grad_match_loss(generated, target, scales=4):
@@ -1202,49 +1239,7 @@ def grad_match_loss(generated, target, scales=4):
     (N, 3, H, W) images, H, W >= 1: a 0-dim fp32 tensor.  `target` is an input image: no gradient."""
     if isinstance(scales, bool) or int(scales) != scales or not 1 <= int(scales) <= 4:
         raise RuntimeError(f"grad_match_loss: scales must be an integer in 1..4, got {scales!r}")
-    if target.requires_grad:
-        raise RuntimeError("grad_match_loss: the target must not require a gradient (only d loss / d generated is computed)")
-    return _GradLossFn.apply(generated, target, int(scales))
-
-
-class _FreqLossFn(torch.autograd.Function):
-    """Focal frequency loss of (generated, target) (csrc/freq_loss.hip); the gradient reaches `generated` only.  The forward keeps
-    the spectrum of generated - target and the plane maxima; the backward reads those, not the images."""
-
-    @staticmethod
-    def forward(ctx, a, b, alpha):
-        lib = _native.lib()
-        if a.shape != b.shape:
-            raise RuntimeError(f"freq_loss: shape mismatch {tuple(a.shape)} vs {tuple(b.shape)}")
-        if a.dim() != 4 or a.shape[1] != 3:
-            raise RuntimeError(f"freq_loss: expected (N, 3, H, W) images, got shape {tuple(a.shape)}")
-        ap, bp = as_phys(a), as_phys(b)
-        n, h, w, _ = ap.shape
-        out = torch.empty((), dtype=torch.float32, device=a.device)
-        need, keep = lib.vcg_freq_loss_workspace(n, h, w), lib.vcg_freq_loss_spectrum(n, h, w)
-        if need == 0 or keep == 0:
-            _native.check(-1, "vcg_freq_loss_workspace")
-        spec = torch.empty(keep // 4, dtype=torch.float32, device=a.device)
-        ws = workspace(need, a.device)
-        _native.check(lib.vcg_freq_loss_fwd(_ptr(ap), _ptr(bp), _ptr(out), n, h, w, alpha, _ptr(spec), keep, _ptr(ws),
-                                            ws.numel() * 4, _stream()), "vcg_freq_loss_fwd")
-        ctx.save_for_backward(spec)
-        ctx.geom = (n, h, w, alpha)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None
-        lib = _native.lib()
-        spec, = ctx.saved_tensors
-        n, h, w, alpha = ctx.geom
-        g = g.contiguous()
-        ga = torch.empty((n, h, w, 4), dtype=torch.float32, device=spec.device)
-        ws = workspace(lib.vcg_freq_loss_workspace(n, h, w), spec.device)
-        _native.check(lib.vcg_freq_loss_bwd(_ptr(spec), spec.numel() * 4, _ptr(g), _ptr(ga), n, h, w, alpha, _ptr(ws),
-                                            ws.numel() * 4, _stream()), "vcg_freq_loss_bwd")
-        return logical_of(ga, 3), None, None
+    return _image_loss(_GradTerm, generated, target, int(scales))
 
 
 def freq_loss(generated, target, alpha=1.0):
@@ -1254,9 +1249,7 @@ def freq_loss(generated, target, alpha=1.0):
     alpha = float(alpha)
     if not math.isfinite(alpha) or alpha < 0.0:
         raise RuntimeError(f"freq_loss: alpha must be finite and >= 0, got {alpha!r}")
-    if target.requires_grad:
-        raise RuntimeError("freq_loss: the target must not require a gradient (only d loss / d generated is computed)")
-    return _FreqLossFn.apply(generated, target, alpha)
+    return _image_loss(_FreqTerm, generated, target, alpha)
 
 
 class _MseConstFn(torch.autograd.Function):

@@ -34,16 +34,21 @@ if __package__ in (None, ""):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     _pkg = importlib.import_module("vae-cyclegan-implementation_amd")
     Networks, ops, parallel, utils, input_pipeline = _pkg.Networks, _pkg.ops, _pkg.parallel, _pkg.utils, _pkg.input_pipeline
+    IMAGE_TERMS = _pkg.Losses.IMAGE_TERMS
 else:
     from . import Networks, input_pipeline, ops, parallel, utils
+    from .Losses import IMAGE_TERMS
 
 ALIASES = {"ae": "autoencoder", "vae_cyclegan": "cyclevaegan"}
 REFERENCE_ARCHS = ["autoencoder", "doubleae", "doublevae", "vae", "aegan", "vaegan", "cycleae", "cyclevae",
                    "cycleaegan", "cyclevaegan"]
 BUILT = tuple(REFERENCE_ARCHS)
-SSIM_ARCHS = ("autoencoder", "vae", "cycleaegan", "cyclevaegan")     # the models whose configure_loss takes lambda_ssim
-FREQ_ARCHS = SSIM_ARCHS                # ... and lambda_freq / freq_alpha (the focal frequency term)
-GRAD_ARCHS = SSIM_ARCHS                # ... and lambda_grad / grad_scales: the term sits wherever the structural one does
+SSIM_ARCHS = ("autoencoder", "vae", "cycleaegan", "cyclevaegan")     # the models whose configure_loss takes Losses.IMAGE_TERMS (named for the first)
+IMAGE_TERM_HELP = {                    # --lambda_<key>, per row of Losses.IMAGE_TERMS
+    "ssim": "weight of the structural term 1 - SSIM",
+    "grad": "weight of the multi-scale gradient-matching term (an L1 on the finite differences of generated - target)",
+    "freq": "weight of the focal frequency term (the weighted squared distance between the 2-D spectra of generated and target)",
+}
 
 
 def create_model(architecture, paired=True, latent_dim=64):
@@ -197,19 +202,8 @@ def clip_bound(text):
     return value
 
 
-def grad_weight(text):
-    """argparse type of --lambda_grad: a finite weight >= 0 (0: off)."""
-    try:
-        value = float(text)
-    except ValueError:
-        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
-    if not math.isfinite(value) or value < 0.0:
-        raise argparse.ArgumentTypeError(f"--lambda_grad must be finite and >= 0 (0: the term is not computed), got {text}")
-    return value
-
-
 def _nonneg(flag, meaning):
-    """argparse type of --lambda_freq / --freq_alpha: a finite number >= 0."""
+    """argparse type of the --lambda_<key> of Losses.IMAGE_TERMS and of --freq_alpha: a finite number >= 0."""
     def parse(text):
         try:
             value = float(text)
@@ -267,16 +261,12 @@ def build_parser():
     p.add_argument("--lambda_identity", type=float, default=5.0)
     p.add_argument("--lambda_cycle", type=float, default=10.0)
     p.add_argument("--lambda_recon", type=float, default=1.0)
-    p.add_argument("--lambda_ssim", type=float, default=0.0,
-                   help="weight of the structural term 1 - SSIM beside the L1 (" + ", ".join(SSIM_ARCHS) + "); 0: not computed")
-    p.add_argument("--lambda_grad", type=grad_weight, default=0.0,
-                   help="weight of the multi-scale gradient-matching term (an L1 on the finite differences of generated - target) "
-                        "beside the L1 (" + ", ".join(GRAD_ARCHS) + "); 0: not computed")
+    for row in IMAGE_TERMS:
+        flag = f"--lambda_{row.key}"
+        p.add_argument(flag, type=_nonneg(flag, " (0: the term is not computed)"), default=0.0,
+                       help=IMAGE_TERM_HELP[row.key] + " beside the L1 (" + ", ".join(SSIM_ARCHS) + "); 0: not computed")
     p.add_argument("--grad_scales", type=int, default=4, choices=(1, 2, 3, 4),
                    help="number of scales of the gradient-matching term; scale s keeps every 2^s-th pixel")
-    p.add_argument("--lambda_freq", type=_nonneg("--lambda_freq", " (0: the term is not computed)"), default=0.0,
-                   help="weight of the focal frequency term (the weighted squared distance between the 2-D spectra of generated "
-                        "and target) beside the L1 (" + ", ".join(FREQ_ARCHS) + "); 0: not computed")
     p.add_argument("--freq_alpha", type=_nonneg("--freq_alpha", ""), default=1.0,
                    help="exponent of the focal frequency term's spectrum weight |difference|^alpha; 0: an unweighted spectral MSE")
     p.add_argument("--clip_grad_norm", type=clip_bound, default=0.0,
@@ -361,27 +351,21 @@ DATASET_MODALITY_DEFAULTS = {                        # reference train.py:367-37
 
 def main(args):
     args.architecture = ALIASES.get(args.architecture, args.architecture)
-    if getattr(args, "lambda_ssim", 0.0) != 0.0 and args.architecture not in SSIM_ARCHS:
-        raise ValueError(f"--lambda_ssim is supported by {', '.join(SSIM_ARCHS)} only, not by {args.architecture}: "
-                         "the flag would be ignored")
-    lambda_grad = getattr(args, "lambda_grad", 0.0)       # (an args object built without the parser)
-    if not math.isfinite(lambda_grad) or lambda_grad < 0.0:
-        raise ValueError(f"--lambda_grad must be finite and >= 0 (0: the term is not computed), got {lambda_grad}")
-    if lambda_grad != 0.0 and args.architecture not in GRAD_ARCHS:
-        raise ValueError(f"--lambda_grad is supported by {', '.join(GRAD_ARCHS)} only, not by {args.architecture}: "
-                         "the flag would be ignored")
-    grad_scales = getattr(args, "grad_scales", 4)
-    if grad_scales not in (1, 2, 3, 4):
-        raise ValueError(f"--grad_scales must be 1, 2, 3 or 4, got {grad_scales}")
-    lambda_freq = getattr(args, "lambda_freq", 0.0)
-    if not math.isfinite(lambda_freq) or lambda_freq < 0.0:
-        raise ValueError(f"--lambda_freq must be finite and >= 0 (0: the term is not computed), got {lambda_freq}")
-    if lambda_freq != 0.0 and args.architecture not in FREQ_ARCHS:
-        raise ValueError(f"--lambda_freq is supported by {', '.join(FREQ_ARCHS)} only, not by {args.architecture}: "
-                         "the flag would be ignored")
-    freq_alpha = getattr(args, "freq_alpha", 1.0)
-    if not math.isfinite(freq_alpha) or freq_alpha < 0.0:
-        raise ValueError(f"--freq_alpha must be finite and >= 0, got {freq_alpha}")
+    image_kw = {}                                    # configure_loss's keywords for the optional image terms
+    for row in IMAGE_TERMS:
+        name = f"lambda_{row.key}"
+        weight = image_kw[name] = getattr(args, name, 0.0)        # (an args object built without the parser)
+        if not math.isfinite(weight) or weight < 0.0:
+            raise ValueError(f"--{name} must be finite and >= 0 (0: the term is not computed), got {weight}")
+        if weight != 0.0 and args.architecture not in SSIM_ARCHS:
+            raise ValueError(f"--{name} is supported by {', '.join(SSIM_ARCHS)} only, not by {args.architecture}: "
+                             "the flag would be ignored")
+        if row.option is not None:
+            image_kw[row.option] = getattr(args, row.option, row.default)
+    if image_kw["grad_scales"] not in (1, 2, 3, 4):
+        raise ValueError(f"--grad_scales must be 1, 2, 3 or 4, got {image_kw['grad_scales']}")
+    if not math.isfinite(image_kw["freq_alpha"]) or image_kw["freq_alpha"] < 0.0:
+        raise ValueError(f"--freq_alpha must be finite and >= 0, got {image_kw['freq_alpha']}")
     clip = getattr(args, "clip_grad_norm", 0.0)
     if not math.isfinite(clip) or clip < 0.0:
         raise ValueError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {clip}")
@@ -449,9 +433,7 @@ def main(args):
     if ema_decay > 0.0 and rank == 0:
         print(f"Averaged generator weights (decay {ema_decay}): the test loss, and with it best_model.pth, is the averaged weights'")
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
-                         lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
-                         lambda_ssim=getattr(args, "lambda_ssim", 0.0), lambda_grad=lambda_grad, grad_scales=grad_scales,
-                         lambda_freq=lambda_freq, freq_alpha=freq_alpha)
+                         lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon, **image_kw)
     if world > 1:
         parallel.attach(model)
     same_xy = args.architecture in ("autoencoder", "vae")
