@@ -490,6 +490,45 @@ size_t vcg_spread_workspace(int N, int H, int W);
 int vcg_spread_display_hw(const float* m2, int count, float gain, float* out_f32, unsigned char* out_u8, float* result, int N,
                           int Hp, int Wp, int top, int left, int H, int W, void* ws, size_t ws_bytes, void* stream);
 
+/* Sliced Wasserstein distance on Laplacian-pyramid patches (new: the reference compares unpaired runs by eye only; Karras et
+   al., ICLR 2018, section 5) — csrc/swd.hip.  Forward only.  No float atomics: every call gives the same bits for the same input.
+   The stages of one pyramid level, in order: vcg_swd_pyramid_level, vcg_swd_gather, vcg_swd_normalize, vcg_swd_project,
+   vcg_sort_columns, vcg_swd_distance.  At most VCG_SWD_MAX_DESC descriptors per set and level: a sorted column lives in LDS. */
+#define VCG_SWD_MAX_DESC 16384
+/* One pyramid level from g, N images (N, S, S, 4) fp32 (channels 0..2 used; `clamp` != 0: clamped to [0, 1] first, level 0).
+   With gk = [1, 4, 6, 4, 1] / 16, K = gk (x) gk and borders mirrored without repeating the edge (-k -> k, S-1+k -> S-1-k):
+     g_next[i, j] = (K * g)[2i, 2j]                          (N, S/2, S/2, 4)
+     lap = g - (4 K) * Z,  Z[2i, 2j] = g_next[i, j], 0 elsewhere   (N, S, S, 4)
+   g_next == NULL: no coarser level; lap = g (clamped if asked).  Channel 3 of both outputs is 0.  S >= 8, even unless g_next is
+   NULL; map sizes that are no multiple of the 32-pixel tile are exact at the borders.  The three buffers are distinct. */
+int vcg_swd_pyramid_level(const float* g, float* g_next, float* lap, int N, int S, int clamp, void* stream);
+/* Rows row_offset .. row_offset + count - 1 of out, a (rows, 147) fp32 matrix: the 7 x 7 x 3 patches of `level` ((N, S, S, 4))
+   named by plan, `count` entries (image, top, left) in HOST memory, read before the call returns; a patch is flattened as
+   (c, dy, dx).  The plan travels in the kernel arguments, 256 entries per launch.  Refused (nothing launched): an entry with
+   image outside [0, N) or top / left outside [0, S - 7]; rows that leave the matrix.  count == 0 is a no-op. */
+int vcg_swd_gather(const float* level, int N, int S, const int32_t* plan, int count, float* out, size_t row_offset,
+                   size_t rows, void* stream);
+/* out = (desc - mean_c) / std_c for the n x 147 descriptor matrix: per channel c (columns 49 c .. 49 c + 48), the mean and the
+   population standard deviation over all n rows and the channel's 49 columns, taken in two passes in double (block slots summed
+   in a fixed order); each element is evaluated in double and rounded once.  A constant channel has std exactly 0: its columns
+   come out NaN.  out may be desc.  ws: vcg_swd_normalize_workspace(n) bytes (0 and vcg_last_error for n outside
+   1 .. VCG_SWD_MAX_DESC), 16-byte aligned. */
+size_t vcg_swd_normalize_workspace(int n);
+int vcg_swd_normalize(const float* desc, float* out, int n, void* ws, size_t ws_bytes, void* stream);
+/* out[j][r] = sum_k dirs[k][j] desc[r][k]: the (ndir, n) TRANSPOSE of desc (n, K) x dirs (K, ndir), so that one direction's
+   projections are contiguous for the sort.  fp32 products and fp32 accumulation (v_mfma_f32_32x32x2_f32). */
+int vcg_swd_project(const float* desc, const float* dirs, float* out, int n, int K, int ndir, void* stream);
+/* Every column of an n x cols fp32 matrix sorted ascending over the rows; element (r, c) is at r * row_stride + c * col_stride
+   in x and in out (dense: row_stride == 1 or col_stride == 1; out may be x).  One workgroup per column: a bitonic network in
+   LDS over the keys padded with +inf to a power of two.  -0 and +0 compare equal; +-inf sort as values.  The network's shape
+   depends on n alone: a column holding a NaN completes, unsorted, and the other columns are not affected.
+   Refused (nothing launched): n outside 1 .. VCG_SWD_MAX_DESC. */
+int vcg_sort_columns(const float* x, float* out, int n, int cols, size_t row_stride, size_t col_stride, void* stream);
+/* out[0] = mean |a[i] - b[i]| over n floats, summed in double: block slots, then a fixed-order final sum.
+   ws: vcg_swd_distance_workspace(n) bytes, 16-byte aligned. */
+size_t vcg_swd_distance_workspace(size_t n);
+int vcg_swd_distance(const float* a, const float* b, float* out, size_t n, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

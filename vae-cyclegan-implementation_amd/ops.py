@@ -1709,3 +1709,136 @@ def spread_display_hw(m2, count, window=None, gain=2.0, uint8=False):
     _native.check(lib.vcg_spread_display_hw(_ptr(as_phys(m2)), int(count), float(gain), _ptr(f32), _ptr(u8), _ptr(res), n, hp, wp, top,
                                             left, h, w, _ptr(ws), ws.numel() * 4, _stream()), "vcg_spread_display_hw")
     return ((f32, u8) if uint8 == "both" else u8 if uint8 else f32), res
+
+
+# ------------------------------------------------------------------ sliced Wasserstein distance (swd.py, csrc/swd.hip)
+SWD_MAX_DESC = 16384              # descriptors per set and level: a sorted column lives in 64 KiB of LDS (VCG_SWD_MAX_DESC)
+SWD_PATCH = 7
+SWD_DESC = 3 * SWD_PATCH * SWD_PATCH
+SWD_MIN_SIDE = 16                 # the coarsest pyramid level
+
+
+def swd_level_sizes(s):
+    """Sides of the Laplacian-pyramid levels of an S x S image: every S / 2^k that is whole and at least 16."""
+    s = int(s)
+    if s < SWD_MIN_SIDE:
+        raise RuntimeError(f"sliced Wasserstein distance: images of {s}x{s} are smaller than the coarsest pyramid level "
+                           f"({SWD_MIN_SIDE}x{SWD_MIN_SIDE})")
+    sizes = [s]
+    while sizes[-1] % 2 == 0 and sizes[-1] // 2 >= SWD_MIN_SIDE:
+        sizes.append(sizes[-1] // 2)
+    return sizes
+
+
+def laplacian_pyramid(images):
+    """Logical (N, 3, S, S) images, S >= 16 -> [L_0 .. L_{L-1}], logical (N, 3, S_k, S_k) nhwc views: the Laplacian pyramid of
+    clamp(images, 0, 1) with the 5-tap binomial kernel and mirrored borders, one launch per level; the last level is the
+    Gaussian residual."""
+    _require_gpu(images, "laplacian_pyramid")
+    g = _images_phys(images, "laplacian_pyramid")
+    n, s = images.shape[0], images.shape[2]
+    sizes = swd_level_sizes(s)
+    lib, out = _native.lib(), []
+    for k, sk in enumerate(sizes):
+        last = k == len(sizes) - 1
+        if last and k > 0:
+            out.append(g)                            # the residual is the previous launch's G
+            break
+        lap = torch.empty((n, sk, sk, 4), dtype=torch.float32, device=images.device)
+        nxt = None if last else torch.empty((n, sk // 2, sk // 2, 4), dtype=torch.float32, device=images.device)
+        _native.check(lib.vcg_swd_pyramid_level(_ptr(g), _ptr(nxt), _ptr(lap), n, sk, 1 if k == 0 else 0, _stream()),
+                      "vcg_swd_pyramid_level")
+        out.append(lap)
+        g = nxt
+    return [logical_of(t, 3) for t in out]
+
+
+def swd_gather(level, plan, out=None, row_offset=0):
+    """The 7x7x3 patches of `level` (logical (N, 3, S, S)) named by `plan`, an int32 host array of (image, top, left) rows, as
+    rows row_offset .. of the (rows, 147) fp32 descriptor matrix `out` (None: a fresh matrix of len(plan) rows).  A patch is
+    flattened as (c, dy, dx).  The plan is read on the host and passed to the kernel by value."""
+    import numpy as np
+    _require_gpu(level, "swd_gather")
+    lp = _images_phys(level, "swd_gather")
+    plan = np.ascontiguousarray(plan, dtype=np.int32)
+    if plan.ndim != 2 or plan.shape[1] != 3:
+        raise RuntimeError(f"swd_gather: the plan must be (count, 3) rows of (image, top, left), got shape {plan.shape}")
+    count = plan.shape[0]
+    if out is None:
+        out = torch.empty((count, SWD_DESC), dtype=torch.float32, device=level.device)
+    _require_gpu(out, "swd_gather")
+    if out.dim() != 2 or out.shape[1] != SWD_DESC or not out.is_contiguous():
+        raise RuntimeError(f"swd_gather: out must be a contiguous (rows, {SWD_DESC}) matrix, got shape {tuple(out.shape)}")
+    _native.check(_native.lib().vcg_swd_gather(_ptr(lp), level.shape[0], level.shape[2], plan.ctypes.data_as(_native._I32P), count,
+                                               _ptr(out), int(row_offset), out.shape[0], _stream()), "vcg_swd_gather")
+    return out
+
+
+def _swd_desc(desc, what):
+    _require_gpu(desc, what)
+    if desc.dim() != 2 or not desc.is_contiguous():
+        raise RuntimeError(f"{what}: expected a contiguous (n, k) matrix, got shape {tuple(desc.shape)}")
+    if not 1 <= desc.shape[0] <= SWD_MAX_DESC:
+        raise RuntimeError(f"{what}: {desc.shape[0]} descriptors (1 .. {SWD_MAX_DESC})")
+
+
+def swd_normalize(desc):
+    """(n, 147) descriptors -> (desc - mean_c) / std_c per channel c (columns 49 c .. 49 c + 48): mean and population standard
+    deviation over all rows and the channel's patch pixels, deterministic (a constant channel comes out NaN)."""
+    _swd_desc(desc, "swd_normalize")
+    if desc.shape[1] != SWD_DESC:
+        raise RuntimeError(f"swd_normalize: expected {SWD_DESC} columns, got {desc.shape[1]}")
+    n = desc.shape[0]
+    ws = torch.empty(_scratch("vcg_swd_normalize_workspace", n) // 4, dtype=torch.float32, device=desc.device)
+    out = torch.empty_like(desc)
+    _call("vcg_swd_normalize", _ptr(desc), _ptr(out), n, _ptr(ws), ws.numel() * 4, _stream())
+    return out
+
+
+def swd_project(desc, directions):
+    """desc (n, k) x directions (k, d) -> the (n, d) projections, fp32 products and sums on the fp32 MFMA.  The result is stored
+    transposed (strides (1, n)): each direction's projections are contiguous, which is what `sort_columns` reads fastest."""
+    _swd_desc(desc, "swd_project")
+    _require_gpu(directions, "swd_project")
+    if directions.dim() != 2 or not directions.is_contiguous() or directions.shape[0] != desc.shape[1]:
+        raise RuntimeError(f"swd_project: directions must be a contiguous ({desc.shape[1]}, d) matrix, got shape "
+                           f"{tuple(directions.shape)}")
+    n, k, d = desc.shape[0], desc.shape[1], directions.shape[1]
+    out = torch.empty((d, n), dtype=torch.float32, device=desc.device)
+    _call("vcg_swd_project", _ptr(desc), _ptr(directions), _ptr(out), n, k, d, _stream())
+    return out.t()
+
+
+def sort_columns(x):
+    """Every column of an (n, cols) fp32 matrix sorted ascending over the rows, n <= 16384: a bitonic network in LDS, one
+    workgroup per column.  x is row-major or the transposed view `swd_project` returns; the result has x's layout."""
+    _require_gpu(x, "sort_columns")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise RuntimeError(f"sort_columns: expected an (n, cols) matrix, got shape {tuple(x.shape)}")
+    n, cols = x.shape
+    if n > SWD_MAX_DESC:
+        raise RuntimeError(f"sort_columns: {n} rows exceed {SWD_MAX_DESC}: a column is sorted in 64 KiB of LDS")
+    if x.is_contiguous():
+        rs, cs = cols, 1
+    elif x.t().is_contiguous():
+        rs, cs = 1, n
+    else:
+        raise RuntimeError("sort_columns: the matrix must be contiguous or the transpose of a contiguous one")
+    out = torch.empty_like(x.t()).t() if rs == 1 else torch.empty_like(x)
+    _call("vcg_sort_columns", _ptr(x), _ptr(out), n, cols, rs, cs, _stream())
+    return out
+
+
+def swd_distance(a, b):
+    """mean |a - b| of two equally laid out matrices, summed in double in a fixed order -> a 0-d fp32 device tensor."""
+    _require_gpu(a, "swd_distance")
+    _require_gpu(b, "swd_distance")
+    if a.shape != b.shape or a.stride() != b.stride() or a.numel() == 0:
+        raise RuntimeError(f"swd_distance: shape / layout mismatch {tuple(a.shape)} {a.stride()} vs {tuple(b.shape)} {b.stride()}")
+    if not (a.is_contiguous() or (a.dim() == 2 and a.t().is_contiguous())):
+        raise RuntimeError("swd_distance: the matrices must be dense")
+    n = a.numel()
+    ws = torch.empty(_scratch("vcg_swd_distance_workspace", n) // 4, dtype=torch.float32, device=a.device)
+    out = torch.empty((), dtype=torch.float32, device=a.device)
+    _call("vcg_swd_distance", _ptr(a), _ptr(b), _ptr(out), n, _ptr(ws), ws.numel() * 4, _stream())
+    return out

@@ -7,7 +7,9 @@ Kept from the reference (test.py:31-70, 457-468, 583-600, 607-726): the flags an
 (dataset type, legacy `paired` / `unpaired` = hypersim, then `<source>_to_<target>`), the figure layouts and the summary keys.
 Added: `--batch_size`, `--seed` (the summer2winter y draws and the VAE eps), `--save_images` (every G(x) as a PNG),
 `--reference_split`, runs of `--dataset synthetic` (their own group, evaluated on the held-out stream train.py validates on),
-and per-image L1 / MSE / PSNR / SSIM against the target on the device (csrc/metrics.hip) for the paired groups.
+per-image L1 / MSE / PSNR / SSIM against the target on the device (csrc/metrics.hip) for the paired groups, and for every
+group, paired or not, the sliced Wasserstein distance between the set {G(x)} and the set {y} (swd.py, csrc/swd.hip; `--no_swd`
+switches it off): the one number an unpaired run gets.
 
 Deliberate differences from the reference:
   * the held-out set is the run's OWN: hypersim is split by `train.split_indices` from the run's --seed and --test_split, as
@@ -36,10 +38,10 @@ if __package__ in (None, ""):
     import importlib
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     _pkg = importlib.import_module("vae-cyclegan-implementation_amd")
-    ops, utils, input_pipeline = _pkg.ops, _pkg.utils, _pkg.input_pipeline
+    ops, utils, input_pipeline, swd = _pkg.ops, _pkg.utils, _pkg.input_pipeline, _pkg.swd
     train = importlib.import_module("vae-cyclegan-implementation_amd.train")
 else:
-    from . import input_pipeline, ops, train, utils
+    from . import input_pipeline, ops, swd, train, utils
 
 GRID_SAMPLES = 8                                   # rows of a per-model grid (test.py:378)
 METRIC_NAMES = ("l1", "mse", "psnr", "ssim")
@@ -61,6 +63,8 @@ def build_parser():
     p.add_argument("--ema", action="store_true",
                    help="evaluate the averaged generator weights of runs trained with --ema_decay (a run without them is reported "
                         "and skipped)")
+    p.add_argument("--no_swd", action="store_true",
+                   help="skip the sliced Wasserstein distance between the translated set and the target set")
     p.add_argument("--reference_split", action="store_true",
                    help="hypersim: evaluate on the reference test.py's random_split(seed 42) subset instead of the run's own")
     return p
@@ -251,9 +255,16 @@ def _finite_or_none(v):
 
 def evaluate_run(model, run, device, args, keep, image_dir=None, paired=True):
     """Translate the run's held-out samples.  Returns (count, host images of the first `keep` samples as (x, y, G(x)) HWC
-    float arrays, per-sample metrics (N, 4) float64 or None, images/s)."""
+    float arrays, per-sample metrics (N, 4) float64 or None, images/s, the sliced Wasserstein entry or None).  The distance is
+    fed (G(x), y) of every batch; its time is not part of images/s."""
     count, batches = held_out_batches(run["args"], run["architecture"], device, args.num_samples, args.batch_size, args.seed,
                                       args.reference_split)
+    dist, dist_time = None, 0.0
+    if not getattr(args, "no_swd", False):
+        try:
+            dist = swd.SlicedWasserstein(run["args"].get("image_size", 256), count, args.seed)
+        except RuntimeError as e:                    # a size the metric refuses: reported, not fatal
+            print(f"  {run['run_name']}: no SWD: {e}")
     ops.manual_seed(args.seed)                       # the eps of every run starts at the same place, whatever ran before
     kept, metrics, done = [], [], 0
     torch.cuda.synchronize(device)
@@ -263,6 +274,12 @@ def evaluate_run(model, run, device, args, keep, image_dir=None, paired=True):
         gx = translate(model, run["architecture"], x)
         if paired:
             metrics.append(ops.image_metrics(gx, y))
+        if dist is not None:
+            torch.cuda.synchronize(device)
+            s0 = time.perf_counter()
+            dist.add(gx, y)
+            torch.cuda.synchronize(device)
+            dist_time += time.perf_counter() - s0
         nb = x.shape[0]
         take = max(0, min(nb, keep - done))
         if take:
@@ -276,8 +293,8 @@ def evaluate_run(model, run, device, args, keep, image_dir=None, paired=True):
         done += nb
     per_sample = torch.cat(metrics).cpu().double().numpy() if metrics else None
     torch.cuda.synchronize(device)
-    ips = done / max(time.perf_counter() - t0, 1e-9)
-    return count, kept, per_sample, ips
+    ips = done / max(time.perf_counter() - t0 - dist_time, 1e-9)
+    return count, kept, per_sample, ips, dist.result() if dist is not None else None
 
 
 def _metrics_entry(per_sample):
@@ -314,9 +331,12 @@ def evaluate_model_group(runs, device, output_dir, args, unpaired=False):
             if args.save_images:
                 image_dir = gdir / "images" / run["run_name"]
                 image_dir.mkdir(parents=True, exist_ok=True)
-            count, kept, per_sample, ips = evaluate_run(model, run, device, args, keep, image_dir, paired=not unpaired)
+            count, kept, per_sample, ips, dist = evaluate_run(model, run, device, args, keep, image_dir, paired=not unpaired)
             print(f"  {run['run_name']}: {count} samples, {ips:.1f} images/s")
-            done.append({"run": run, "count": count, "kept": kept, "per_sample": per_sample})
+            if dist is not None:
+                print(f"  {run['run_name']}: SWD x1e3 " + " ".join(f"{k}: {'n/a' if v is None else format(v, '.2f')}"
+                                                                  for k, v in list(dist["levels"].items()) + [("mean", dist["mean"])]))
+            done.append({"run": run, "count": count, "kept": kept, "per_sample": per_sample, "swd": dist})
             del model
         if not done:
             print("No models loaded successfully for this group!")
@@ -336,6 +356,8 @@ def evaluate_model_group(runs, device, output_dir, args, unpaired=False):
             models.append({"name": d["run"]["run_name"], "architecture": d["run"]["architecture"],
                            "checkpoint": str(d["run"]["best_model_path"]), "training_args": d["run"]["args"],
                            "metrics": means, "per_sample": lists})
+            if not getattr(args, "no_swd", False):
+                models[-1]["swd"] = d["swd"]
         summary = {"modality": key, "source_modality": ref["source_modality"], "target_modality": ref["target_modality"],
                    "num_models": len(done), "num_samples": done[0]["count"], "unpaired": unpaired, "models": models}
         with open(gdir / "summary.json", "w") as f:
