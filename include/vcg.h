@@ -529,6 +529,66 @@ int vcg_sort_columns(const float* x, float* out, int n, int cols, size_t row_str
 size_t vcg_swd_distance_workspace(size_t n);
 int vcg_swd_distance(const float* a, const float* b, float* out, size_t n, void* ws, size_t ws_bytes, void* stream);
 
+/* Sliced Wasserstein distance as a training loss between two image sets (new: a patch-distribution term that needs no pairing,
+   no discriminator and no pretrained network) — csrc/swd_loss.hip; DESIGN.md, "Sliced Wasserstein training loss".  No float
+   atomics: every call gives the same bits for the same input.  The stages of one level, forward: [vcg_swd_pool,]
+   vcg_swd_grid_gather, vcg_swd_project, vcg_sort_columns_indexed (the generated set) / vcg_sort_columns (the target set),
+   vcg_swd_pair_loss; backward: vcg_swd_project with the roles swapped, vcg_swd_grid_scatter, vcg_swd_pool_adjoint_add.
+   Images are (N, H, W, 4) fp32 with channels 0..2 used.  At most VCG_SWD_LOSS_MAX_DESC descriptors per set and level: a column's
+   keys and source rows are sorted together in 64 KiB of LDS. */
+#define VCG_SWD_LOSS_MAX_DESC 8192
+#define VCG_SWD_LOSS_MAX_LEVELS 3
+/* The number of levels, at most VCG_SWD_LOSS_MAX_LEVELS, an H x W image has: level k + 1 exists while both sides of level k are
+   even and their halves at least 16.  0 and vcg_last_error: a side under 16 or over 32768.  Host arithmetic. */
+int vcg_swd_loss_levels(int H, int W);
+/* The side s of the square cells an (N, H, W) level is cut into: the smallest s >= 8 with N floor(H / s) floor(W / s) <=
+   VCG_SWD_LOSS_MAX_DESC.  0 and vcg_last_error: N < 1, a side under 16 or over 32768, or no s <= min(H, W) meets the cap.
+   Host arithmetic. */
+int vcg_swd_cell_side(int N, int H, int W);
+/* out (N, H/2, W/2, 4) = the 2 x 2 mean of x (N, H, W, 4): the four values added in double, rounded once; channel 3 is 0.
+   vcg_swd_pool_adjoint_add: fine (N, H, W, 4) += coarse (N, H/2, W/2, 4) / 4 at [y/2, x/2], channel 3 left alone.
+   Refused (nothing launched): a null pointer; N outside 1..65535; an odd side, a half under 16, a side over 32768; buffers that
+   are not 16-byte aligned or not distinct. */
+int vcg_swd_pool(const float* x, float* out, int N, int H, int W, void* stream);
+int vcg_swd_pool_adjoint_add(const float* coarse, float* fine, int N, int H, int W, void* stream);
+/* The level (N, H, W, 4) is cut into cy x cx = floor(H / s) x floor(W / s) cells of s x s per image; cell (image, i, j) gives row
+   (image cy + i) cx + j of out, an (N cy cx, 147) matrix: the 7 x 7 x 3 patch whose top left pixel is (i s + oy, j s + ox),
+   flattened as (c, dy, dx).  Rows and columns past cy s, cx s belong to no cell.  The geometry travels by value: no host
+   memory is read.
+   vcg_swd_grid_scatter is the adjoint in gather form: out (N, H, W, 4) [pixel of patch element e of row r][c] =
+   gdesc[r][e] * scale * (gscale ? gscale[0] : 1), gscale a device scalar; every other pixel and channel 3 are +0: it clears
+   the map as it writes it.
+   Refused (nothing launched): a null level / gdesc / out; N outside 1..65535; a side under 16 or over 32768; s under 8 or over
+   min(H, W); oy or ox outside [0, s - 7]; N cy cx outside 1 .. VCG_SWD_LOSS_MAX_DESC; a scale that is not finite; out of the
+   scatter not 16-byte aligned. */
+int vcg_swd_grid_gather(const float* level, float* out, int N, int H, int W, int s, int oy, int ox, void* stream);
+int vcg_swd_grid_scatter(const float* gdesc, const float* gscale, float scale, float* out, int N, int H, int W, int s, int oy,
+                         int ox, void* stream);
+/* vcg_sort_columns that remembers where each key came from: keys and rows (int32) have x's layout; column c of keys is column c
+   of x ascending, rows[i] the row of x that keys[i] came from.  Pairs are ordered by (key, row): the result is that of a stable
+   argsort.  One workgroup per column, a bitonic network in LDS over the pairs padded with (+inf, n ..) to a power of two; its
+   shape depends on n alone.  A column holding a NaN completes and comes out as it came, rows = 0 .. n - 1: the rows of a
+   column are a permutation of 0 .. n - 1 in every case, and the other columns are not affected.  keys may be x.
+   Refused (nothing launched): a null pointer; n outside 1 .. VCG_SWD_LOSS_MAX_DESC; cols < 1; strides that are not those of a
+   dense matrix; keys == rows. */
+int vcg_sort_columns_indexed(const float* x, float* keys, int32_t* rows, int n, int cols, size_t row_stride, size_t col_stride,
+                             void* stream);
+/* One pass over a_sorted, b_sorted and perm_a, all (ndir, n) with a direction's n values contiguous:
+     level = mean_{d,i} |a_sorted[d][i] - b_sorted[d][i]|, summed in double in block slots, then in a fixed order;
+     total[0] = (accumulate ? total[0] : 0) + weight * level (a double on the device), out[0] = (float)total[0];
+     gproj[d][perm_a[d][i]] = sign(a_sorted[d][i] - b_sorted[d][i]), sign(0) = 0, not scaled (an entry of perm_a outside
+     [0, n) is skipped).
+   ws: vcg_swd_pair_loss_workspace(n, ndir) bytes (0 and vcg_last_error on refused arguments), 16-byte aligned.
+   Refused (nothing launched): a null pointer; n outside 1 .. VCG_SWD_LOSS_MAX_DESC; ndir outside 1..1024; a weight that is not
+   finite; gproj aliasing an input; a workspace that is too small or misaligned. */
+size_t vcg_swd_pair_loss_workspace(int n, int ndir);
+int vcg_swd_pair_loss(const float* a_sorted, const float* b_sorted, const int32_t* perm_a, float* gproj, int n, int ndir,
+                      double weight, int accumulate, double* total, float* out, void* ws, size_t ws_bytes, void* stream);
+/* out = x, a (K, D) row-major matrix, with every column scaled to unit 2-norm: the sum of squares in double, each element
+   evaluated in double and rounded once (a zero column comes out NaN).  One workgroup per column.  out may be x.
+   Refused (nothing launched): a null pointer; K outside 1..65536; D outside 1..65535. */
+int vcg_swd_unit_columns(const float* x, float* out, int K, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

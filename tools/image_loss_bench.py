@@ -10,7 +10,11 @@ A kernel time is the median over 15 rounds of (HIP-event time of 20 back-to-back
 more call costs a stream that is already busy, which is how the step sees it.  Writes OUT/<term>_loss_bench.txt (OUT defaults to
 profiles_out) and prints the same.
 
-    python tools/image_loss_bench.py <ssim|grad|freq>            # STEP=0: kernels only
+swd (the sliced Wasserstein term, DESIGN.md "Sliced Wasserstein training loss") has no single forward / backward entry: its
+stage calls are timed one by one through ops on the level-0 tensors of the same batch, then ops.swd_loss (3 levels) forward and
+forward + backward, then the step with lambda_swd 0 and 1.
+
+    python tools/image_loss_bench.py <ssim|grad|freq|swd>        # STEP=0: kernels only
 """
 import ctypes
 import importlib
@@ -29,7 +33,8 @@ dev = torch.device("cuda:0")
 HBM = 6.3e12          # practical bytes / s
 PEAK = 157.3e12       # fp32 MFMA, FLOP / s
 TILE, CHUNK = 64, 32  # csrc/freq_loss.hip: FF_TM = FF_TN, FF_TK
-SHAPES = {"ssim": [(8, 256, 256), (2, 32, 32)], "grad": [(8, 256, 256)], "freq": [(8, 256, 256)]}
+SHAPES = {"ssim": [(8, 256, 256), (2, 32, 32)], "grad": [(8, 256, 256)], "freq": [(8, 256, 256)], "swd": [(8, 256, 256)]}
+ON_WEIGHT = {"swd": 1.0}          # the weight of the "on" step; 0.5 for the others
 lines = []
 
 
@@ -118,6 +123,56 @@ def kernels(term, n, h, w, rounds=15, warm=3):
     say()
 
 
+def swd_kernels(n, h, w, rounds=15, warm=3):
+    """The stages of one level (level 0: the largest), then the whole term over 3 levels."""
+    loss = pkg.Losses.SlicedWassersteinLoss(levels=3, seed=1)
+    a = ops.to_nhwc(ops.rand_uniform((n, 3, h, w), dev, seed=1))
+    b = ops.to_nhwc(ops.rand_uniform((n, 3, h, w), dev, seed=2))
+    ap, dirs = ops.as_phys(a), loss.directions(dev, 0)
+    s = ops.swd_cell_side(n, h, w)
+    desc = ops.swd_grid_gather(ap, s, 1, 0)
+    proj = ops.swd_project(desc, dirs)
+    keys, rows = ops.sort_columns_indexed(proj)
+    other = ops.sort_columns(ops.swd_project(ops.swd_grid_gather(ops.as_phys(b), s, 1, 0), dirs))
+    _, gproj, _ = ops.swd_pair_loss(keys, other, rows)
+    gdesc = ops.swd_project(dirs, gproj).t()
+    fine, coarse = torch.zeros_like(ap), ops.swd_pool(ap)
+    g = torch.ones((), dtype=torch.float32, device=dev)
+    nd = desc.shape[0]
+    a_req = a.detach().clone().requires_grad_(True)
+
+    def whole(backward):
+        v = ops.swd_loss(a_req if backward else a, b, 3, ops.SwdPlan(loss.offsets(n, h, w, 0), dirs))
+        if backward:
+            a_req.grad = None
+            v.backward()
+
+    runs = [
+        ("swd_pool", lambda: ops.swd_pool(ap)),
+        ("swd_grid_gather", lambda: ops.swd_grid_gather(ap, s, 1, 0)),
+        ("swd_project", lambda: ops.swd_project(desc, dirs)),
+        ("sort_columns_indexed", lambda: ops.sort_columns_indexed(proj)),
+        ("sort_columns", lambda: ops.sort_columns(proj)),
+        ("swd_pair_loss", lambda: ops.swd_pair_loss(keys, other, rows)),
+        ("swd_project (transposed)", lambda: ops.swd_project(dirs, gproj)),
+        ("swd_grid_scatter", lambda: ops.swd_grid_scatter(gdesc, (n, h, w), s, 1, 0, 1.0 / nd, g)),
+        ("swd_pool_adjoint_add", lambda: ops.swd_pool_adjoint_add(coarse, fine)),
+        ("swd_loss forward, 3 levels", lambda: whole(False)),
+        ("swd_loss fwd + bwd, 3 levels", lambda: whole(True)),
+    ]
+    ts = {name: [] for name, _ in runs}
+    for i in range(warm + rounds):
+        for name, fn in runs:
+            us = timed_us(fn, calls=10)
+            if i >= warm:
+                ts[name].append(us)
+    say(f"{n} x 3 x {h} x {w}: cells of {s}x{s}, {nd} descriptors per set on level 0, {dirs.shape[1]} directions")
+    say(f"  {'stage (ops call, allocation included)':40s} {'us / call':>10s} {'min .. max':>17s}")
+    for name, _ in runs:
+        say(f"  {name:40s} {statistics.median(ts[name]):10.2f} {min(ts[name]):8.2f} ..{max(ts[name]):7.2f}")
+    say()
+
+
 def step_ms(model, batch, steps=10, warm=3):
     for _ in range(warm):
         model.training_step(batch)
@@ -131,17 +186,18 @@ def step_ms(model, batch, steps=10, warm=3):
 
 def steps(term):
     models = {}
-    for lam in (0.0, 0.5):
+    on = ON_WEIGHT.get(term, 0.5)
+    for lam in (0.0, on):
         torch.manual_seed(3)
         m = pkg.Networks.CycleVAEGAN(latent_dim=64, paired=False).to(dev).train()
         m.configure_optimizers(lr=2e-4)
         m.configure_loss(**{f"lambda_{term}": lam})
         models[lam] = m
     batch = {"x": ops.rand_uniform((8, 3, 256, 256), dev, seed=11), "y": ops.rand_uniform((8, 3, 256, 256), dev, seed=12)}
-    say(f"cyclevaegan 256^2 batch 8 unpaired, ms / step (10 steps after 3 warm-up), lambda_{term} 0 | 0.5, alternated")
+    say(f"cyclevaegan 256^2 batch 8 unpaired, ms / step (10 steps after 3 warm-up), lambda_{term} 0 | {on:g}, alternated")
     for rnd in range(3):
-        r = {lam: step_ms(models[lam], batch) for lam in (0.0, 0.5)}
-        say(f"  round {rnd}: {r[0.0]:7.2f} | {r[0.5]:7.2f}   ({(r[0.5] / r[0.0] - 1) * 100:+.2f} %)")
+        r = {lam: step_ms(models[lam], batch) for lam in (0.0, on)}
+        say(f"  round {rnd}: {r[0.0]:7.2f} | {r[on]:7.2f}   ({(r[on] / r[0.0] - 1) * 100:+.2f} %)")
 
 
 if __name__ == "__main__":
@@ -150,7 +206,10 @@ if __name__ == "__main__":
     term = sys.argv[1]
     say(f"# tools/image_loss_bench.py {term} on {torch.cuda.get_device_name(0)}")
     for shape in SHAPES[term]:
-        kernels(term, *shape)
+        if term == "swd":
+            swd_kernels(*shape)
+        else:
+            kernels(term, *shape)
     if os.environ.get("STEP", "1") != "0":
         steps(term)
     out = os.environ.get("OUT", os.path.join(ROOT, "profiles_out"))

@@ -1,7 +1,7 @@
 """Atomic losses with the reference's class surface (Losses.py:14-121 of the reference),
 each reduction a HIP kernel (wavefront shuffle -> block partial -> ordered final sum).
 
-Only the six atomic classes (and StructuralLoss, GradientMatchingLoss and FocalFrequencyLoss, which the reference lacks) exist here: the reference's composite loss classes
+Only the six atomic classes (and StructuralLoss, GradientMatchingLoss, FocalFrequencyLoss and SlicedWassersteinLoss, which the reference lacks) exist here: the reference's composite loss classes
 (Losses.py:123-379) are dead code there and are not part of the training step.
 """
 import math
@@ -86,6 +86,63 @@ IMAGE_TERMS = (
     ImageTerm("grad", GradientMatchingLoss, "grad_scales", 4),
     ImageTerm("freq", FocalFrequencyLoss, "freq_alpha", 1.0),
 )
+
+
+class SlicedWassersteinLoss(nn.Module):
+    """Sliced Wasserstein distance between the 7x7x3 patch sets of `generated` and `target` over `levels` in 1..3 levels of a
+    2 x 2 box pyramid (ops.swd_loss; new: the reference has no distribution term).  It needs no pairing: a term for G(x) against
+    the SET of y.
+
+    Every call draws a fresh plan from the loss's own step counter: the per-level patch offsets from
+    numpy.random.RandomState([seed, step]) on the host, the 128 unit directions on the device from vcg_randn at
+    (DIRECTION_STREAM ^ seed, step * the draws of one matrix) — a seed stream of its own, so a run with the term on consumes the
+    eps stream (ops.manual_seed) exactly as one with it off, and nothing crosses PCIe or synchronises.  state_dict() carries the
+    seed and the counter: a resumed run continues the sequence."""
+    DIRECTION_STREAM = 0x5D1CED5EED000000          # keeps the directions' Philox key apart from ops.manual_seed's small seeds
+    DIRECTION_QUADS = (ops.SWD_DESC * ops.SWD_LOSS_DIRS + 3) // 4
+
+    def __init__(self, levels=3, seed=0):
+        super().__init__()
+        if isinstance(levels, bool) or int(levels) != levels or not 1 <= int(levels) <= ops.SWD_LOSS_MAX_LEVELS:
+            raise ValueError(f"levels must be an integer in 1..{ops.SWD_LOSS_MAX_LEVELS}, got {levels!r}")
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2 ** 32:
+            raise ValueError(f"seed must be an integer in 0..2^32-1, got {seed!r}")
+        self.levels = int(levels)
+        self.seed = int(seed)
+        self.step = 0
+
+    def offsets(self, n_images, h, w, step=None):
+        """((oy, ox) per level) of call number `step` (None: the next one) on `n_images` H x W images: uniform on [0, s_k - 7]^2."""
+        import numpy as np
+        rng = np.random.RandomState([self.seed, self.step if step is None else int(step)])
+        return tuple((int(rng.randint(s - ops.SWD_PATCH + 1)), int(rng.randint(s - ops.SWD_PATCH + 1)))
+                     for _, _, s, _ in ops.swd_loss_geometry(n_images, h, w, self.levels))
+
+    def directions(self, device, step=None):
+        """The (147, 128) unit directions of call number `step` (None: the next one), drawn and normalised on `device`."""
+        step = self.step if step is None else int(step)
+        gauss = ops.randn((ops.SWD_DESC, ops.SWD_LOSS_DIRS), device, self.DIRECTION_STREAM ^ self.seed, step * self.DIRECTION_QUADS)
+        return ops.swd_unit_columns(gauss)
+
+    def draw(self, generated):
+        """The plan of the next call on images shaped like `generated`; advances the counter."""
+        n, _, h, w = generated.shape
+        plan = ops.SwdPlan(self.offsets(n, h, w), self.directions(generated.device))
+        self.step += 1
+        return plan
+
+    def forward(self, generated, target):
+        if generated.dim() != 4:
+            raise RuntimeError(f"swd_loss: expected (N, 3, H, W) images, got shape {tuple(generated.shape)}")
+        return ops.swd_loss(generated, target, self.levels, self.draw(generated))
+
+    def get_extra_state(self):
+        return {"seed": self.seed, "step": self.step, "levels": self.levels}
+
+    def set_extra_state(self, state):
+        if int(state["levels"]) != self.levels:
+            raise ValueError(f"the saved sliced Wasserstein loss has {state['levels']} levels, this one {self.levels}")
+        self.seed, self.step = int(state["seed"]), int(state["step"])
 
 
 class GANLossGenerator(nn.Module):

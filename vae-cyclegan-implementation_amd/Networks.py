@@ -20,7 +20,7 @@ from torch.nn.utils import spectral_norm
 
 from . import ops
 from .Losses import (IMAGE_TERMS, CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss, KLDivergenceLoss,
-                     TranslationLoss)
+                     SlicedWassersteinLoss, TranslationLoss)
 from .image_pool import ImagePool, pool_seed as _pool_seed
 from .optim import FusedAdam
 
@@ -414,6 +414,65 @@ def _eval_image_terms(terms, pairs):
     return named, weights
 
 
+SWD_MODELS = "cycleae, cyclevae, cycleaegan and cyclevaegan"      # the models with two translation directions and two image sets
+
+
+def _swd_weight(kwargs):
+    lam = float(kwargs.get("lambda_swd", 0.0))
+    if not math.isfinite(lam) or lam < 0.0:
+        raise ValueError(f"lambda_swd must be finite and >= 0, got {lam}")
+    return lam
+
+
+def _refuse_swd(model, kwargs):
+    """configure_loss of the single-direction models takes the keyword so that one call fits every architecture: 0 is ignored."""
+    lam = _swd_weight(kwargs)
+    if lam != 0.0:
+        raise ValueError(f"lambda_swd={lam}: {type(model).__name__} translates in one direction; the sliced Wasserstein term is "
+                         f"built into {SWD_MODELS}")
+
+
+class _SwdMixin:
+    """The sliced Wasserstein term of a cycle model whose configure_loss was given lambda_swd > 0: lambda_swd (swd(G(x), y) +
+    swd(F(y), x)), a distance between the patch distributions of the translated batch and of the other domain's batch
+    (Losses.SlicedWassersteinLoss).  It is the one term of the unpaired objectives that looks at G(x) against domain Y without a
+    discriminator.  With the weight at its default 0 `swd_term` is None: no loss object exists, and the step computes, launches,
+    draws and reports exactly what it did before the term was added."""
+    swd_term = None                               # (weight, SlicedWassersteinLoss)
+
+    def _configure_swd(self, kwargs):
+        lam = _swd_weight(kwargs)
+        self.swd_term = None if lam == 0.0 else (lam, SlicedWassersteinLoss(levels=kwargs.get("swd_levels", 3),
+                                                                              seed=kwargs.get("swd_seed", 0)))
+
+    @property
+    def swd_enabled(self):
+        return self.swd_term is not None
+
+    def _add_swd(self, t, terms, weights, Gx, Fy, x, y):
+        """Appends the term to the generator objective's (terms, weights) and to the step's scalars `t`; on the main stream, after
+        the direction join."""
+        if self.swd_term is not None:
+            lam, fn = self.swd_term
+            t["loss_swd"] = ops.weighted_sum([fn(Gx, y), fn(Fy, x)], [1.0, 1.0])
+            terms.append(t["loss_swd"])
+            weights.append(lam)
+
+    def _swd_spec(self):
+        return _same("loss_swd") if self.swd_term is not None else ()
+
+    def save_swd_state(self):
+        """The loss's seed and step counter — what a checkpoint stores under `vcg_swd_loss`."""
+        if self.swd_term is None:
+            raise RuntimeError("save_swd_state(): this model has no sliced Wasserstein term (configure_loss(lambda_swd=...))")
+        return self.swd_term[1].state_dict()
+
+    def load_swd_state(self, state):
+        if self.swd_term is None:
+            raise RuntimeError("load_swd_state(): this model has no sliced Wasserstein term (configure_loss(lambda_swd=...))")
+        self.swd_term[1].load_state_dict(state)
+
+
 def _backward_and_step(loss, optimizer, reducer):
     """zero_grad -> backward -> [data-parallel gradient exchange, its buckets launched from inside the backward] -> step."""
     optimizer.zero_grad()
@@ -628,6 +687,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         return self._single_optimizer(params, lr, betas, clip_grad_norm, ema_decay, pool_size)
 
     def configure_loss(self, **kwargs):
+        _refuse_swd(self, kwargs)
         self.loss_fn = TranslationLoss()
         self.image_terms = _image_terms(kwargs)
 
@@ -731,6 +791,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         return self._single_optimizer(self.parameters(), lr, betas, clip_grad_norm, ema_decay, pool_size)
 
     def configure_loss(self, **kwargs):
+        _refuse_swd(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
         self.loss_kl_fn = KLDivergenceLoss()
         self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
@@ -861,7 +922,7 @@ def _discriminate(DY, DX, Gx, Fy, x, y, fork=None):
     return DYGx, DXFy, DXx, DYy
 
 
-class CycleVAEGAN(_GanMixin, nn.Module):
+class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
     """Two VAEs (G: X->Y, F: Y->X) + two discriminators; cycle + LSGAN + KL (+identity if paired);
     alternating G then D update  (reference Networks.py:1872-2150).
 
@@ -938,6 +999,7 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
         self.image_terms = _image_terms(kwargs)
+        self._configure_swd(kwargs)
 
     def _check_configured(self, need_opt=True):
         if (self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None
@@ -998,7 +1060,9 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         # the optional cycle terms, each on the L1 cycle term's operands; FGx and GFy are joined by now, as for loss_cycle
         extra, extra_weights = _eval_image_terms(self.image_terms, [(FGx, x), (GFy, y)])
         t.update(extra)
-        t["G_loss"] = ops.weighted_sum(terms + list(extra.values()), weights + extra_weights)
+        terms, weights = terms + list(extra.values()), weights + extra_weights
+        self._add_swd(t, terms, weights, Gx, Fy, x, y)     # the translated batches against the other domain's: needs no pairing
+        t["G_loss"] = ops.weighted_sum(terms, weights)
         # discriminator objective on the SAME discriminator outputs (reference :2038-2040)
         t["D_loss_x_real"], _ = ops.mse_const(DXx, 1.0)
         t["D_loss_x_fake"], _ = ops.mse_const(DXFy, 0.0)
@@ -1018,7 +1082,7 @@ class CycleVAEGAN(_GanMixin, nn.Module):
         if self.paired:
             keys += ("loss_identity",)
         keys += tuple(name for name, _, _ in self.image_terms)
-        return (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + (() if training else _GX_FY)
+        return (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + self._swd_spec() + (() if training else _GX_FY)
 
     def _pooled_d_terms(self, t, Gx, Fy):
         """The discriminators' fake terms with image history pools (_PoolMixin), after the forward (both direction streams are
@@ -1084,7 +1148,7 @@ class CycleAEGAN(CycleVAEGAN):
         return Gx, FGx, Fy, GFy, self.DY(Gx), self.DX(Fy), self.DX(x), self.DY(y), Gy, Fx
 
 
-class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
+class _CycleNoGAN(_SwdMixin, _OptimizerStatesMixin, nn.Module):
     """Two generators G: X->Y, F: Y->X trained on the cycle loss alone (+ KL for VAEs, + translation loss when paired),
     one Adam over both — the shared body of CycleAE and CycleVAE (reference Networks.py:1350-1616)."""
 
@@ -1140,13 +1204,15 @@ class _CycleNoGAN(_OptimizerStatesMixin, nn.Module):
             t["loss_trans"] = ops.weighted_sum([self.loss_trans(Gx, y), self.loss_trans(Fy, x)], [1.0, 1.0])
             terms.append(t["loss_trans"])
             weights.append(1.0)
-        t["G_loss"] = ops.weighted_sum(terms, weights)
+        self._add_swd(t, terms, weights, Gx, Fy, x, y)     # unpaired, the one term that ties G(x) to domain Y (G = F = identity
+        t["G_loss"] = ops.weighted_sum(terms, weights)     # satisfies the cycle loss exactly)
         return t, Gx, Fy
 
     def _report_spec(self, training):
-        """the reference's key order (:1421-1433, :1547-1561): total_loss, loss_cycle, [loss_kl], G_loss, [Gx, Fy], [loss_trans]"""
+        """the reference's key order (:1421-1433, :1547-1561): total_loss, loss_cycle, [loss_kl], G_loss, [Gx, Fy], [loss_trans],
+        then [loss_swd]"""
         return ((("total_loss", "G_loss"),) + _same("loss_cycle", *(("loss_kl",) if self._variational else ()), "G_loss")
-                + (() if training else _GX_FY) + (_same("loss_trans") if self.paired else ()))
+                + (() if training else _GX_FY) + (_same("loss_trans") if self.paired else ()) + self._swd_spec())
 
     def training_step(self, batch):
         _refuse_training_in_ema_scope(self)
@@ -1177,6 +1243,7 @@ class CycleAE(_CycleNoGAN):
         if self.paired:
             self.loss_trans = TranslationLoss()
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
+        self._configure_swd(kwargs)
 
 
 class CycleVAE(_CycleNoGAN):
@@ -1197,6 +1264,7 @@ class CycleVAE(_CycleNoGAN):
         self.loss_kl = KLDivergenceLoss()
         self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
+        self._configure_swd(kwargs)
 
 
 class _DoubleStep(_OptimizerStatesMixin, nn.Module):
@@ -1266,6 +1334,7 @@ class DoubleAutoencoder(_DoubleStep):
         return cycle_ae
 
     def configure_loss(self, **kwargs):
+        _refuse_swd(self, kwargs)
         self.loss_fn = TranslationLoss()
 
     def _check_configured(self, need_opt=True):
@@ -1368,6 +1437,7 @@ class DoubleVariationalAutoencoder(_DoubleStep):
         return cycle_vae
 
     def configure_loss(self, **kwargs):
+        _refuse_swd(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
         self.loss_kl_fn = KLDivergenceLoss()
         self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
@@ -1470,6 +1540,7 @@ class AEGAN(_SingleGAN):
         return Gx, Gy, self.D(Gx), self.D(y)
 
     def configure_loss(self, **kwargs):
+        _refuse_swd(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
         self.loss_gan_gen_fn = GANLossGenerator()
         self.loss_gan_disc_fn = GANLossDiscriminator()
@@ -1529,6 +1600,7 @@ class VAEGAN(_SingleGAN):
         return Gx, mu, logvar, Gy, mu_y, logvar_y, self.D(Gx), self.D(y)
 
     def configure_loss(self, **kwargs):
+        _refuse_swd(self, kwargs)
         self.translation_loss = TranslationLoss()
         self.gan_loss_gen = GANLossGenerator()
         self.gan_loss_disc = GANLossDiscriminator()

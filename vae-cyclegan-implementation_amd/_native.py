@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # VCG_LIBVCG: load another build of the same sources (A/B runs of kernel variants, tools/); the default is the in-tree library
 LIB_PATH = os.environ.get("VCG_LIBVCG") or os.path.join(_HERE, "libvcg.so")
-SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip"]
+SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip", "swd_loss.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vcg.h")
 
 _c = ctypes
@@ -19,6 +19,7 @@ _P = _c.c_void_p
 _I = _c.c_int
 _Z = _c.c_size_t
 _F = _c.c_float
+_D = _c.c_double
 _U64 = _c.c_uint64
 _I32P = _c.POINTER(_c.c_int32)
 _U64P = _c.POINTER(_c.c_uint64)
@@ -120,6 +121,16 @@ SIGNATURES = {
     "vcg_sort_columns": (_I, [_P, _P, _I, _I, _Z, _Z, _P]),
     "vcg_swd_distance_workspace": (_Z, [_Z]),
     "vcg_swd_distance": (_I, [_P, _P, _P, _Z, _P, _Z, _P]),
+    "vcg_swd_loss_levels": (_I, [_I, _I]),
+    "vcg_swd_cell_side": (_I, [_I, _I, _I]),
+    "vcg_swd_pool": (_I, [_P, _P, _I, _I, _I, _P]),
+    "vcg_swd_pool_adjoint_add": (_I, [_P, _P, _I, _I, _I, _P]),
+    "vcg_swd_grid_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "vcg_swd_grid_scatter": (_I, [_P, _P, _F, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "vcg_sort_columns_indexed": (_I, [_P, _P, _P, _I, _I, _Z, _Z, _P]),
+    "vcg_swd_pair_loss_workspace": (_Z, [_I, _I]),
+    "vcg_swd_pair_loss": (_I, [_P, _P, _P, _P, _I, _I, _D, _I, _P, _P, _P, _Z, _P]),
+    "vcg_swd_unit_columns": (_I, [_P, _P, _I, _I, _P]),
 }
 
 _lib = None

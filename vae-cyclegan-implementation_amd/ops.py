@@ -10,6 +10,7 @@ import ctypes
 import os
 import weakref
 import math
+from typing import NamedTuple
 
 import torch
 
@@ -1842,3 +1843,241 @@ def swd_distance(a, b):
     out = torch.empty((), dtype=torch.float32, device=a.device)
     _call("vcg_swd_distance", _ptr(a), _ptr(b), _ptr(out), n, _ptr(ws), ws.numel() * 4, _stream())
     return out
+
+
+# ------------------------------------------------------------------ sliced Wasserstein training loss (csrc/swd_loss.hip)
+SWD_LOSS_MAX_DESC = 8192          # descriptors per set and level: keys and source rows of a column, 64 KiB of LDS (VCG_SWD_LOSS_MAX_DESC)
+SWD_LOSS_MAX_LEVELS = 3
+SWD_LOSS_DIRS = 128               # directions per step
+
+
+class SwdPlan(NamedTuple):
+    """What one evaluation of `swd_loss` draws: the in-cell patch offset (oy, ox) of every level, and the (147, 128) matrix of
+    unit directions on the device (Losses.SlicedWassersteinLoss draws both)."""
+    offsets: tuple
+    directions: torch.Tensor
+
+
+def _swd_int(value, name, what):
+    if isinstance(value, bool) or not hasattr(value, "__index__"):
+        raise RuntimeError(f"{what}: {name} must be an integer, got {value!r}")
+    return int(value)
+
+
+def swd_loss_levels(h, w):
+    """How many levels (at most 3) the loss has on H x W images: level k + 1 is the 2 x 2 mean of level k and exists while both
+    sides of level k are even and their halves at least 16."""
+    levels = _native.lib().vcg_swd_loss_levels(_swd_int(h, "h", "swd_loss_levels"), _swd_int(w, "w", "swd_loss_levels"))
+    if levels == 0:
+        _native.check(-1, "vcg_swd_loss_levels")
+    return levels
+
+
+def swd_cell_side(n_images, h, w):
+    """The side s of the cells a level of `n_images` H x W maps is cut into: the smallest s >= 8 that leaves at most 8192 cells
+    (one descriptor each) in the set."""
+    s = _native.lib().vcg_swd_cell_side(*(_swd_int(v, k, "swd_cell_side") for k, v in (("n_images", n_images), ("h", h), ("w", w))))
+    if s == 0:
+        _native.check(-1, "vcg_swd_cell_side")
+    return s
+
+
+def _swd_phys(t, what):
+    _require_gpu(t, what)
+    if t.dim() != 4 or t.shape[3] != 4 or not t.is_contiguous():
+        raise RuntimeError(f"{what}: expected a contiguous physical (N, H, W, 4) image tensor, got shape {tuple(t.shape)}")
+    return t.shape[0], t.shape[1], t.shape[2]
+
+
+def swd_pool(x):
+    """Physical (N, H, W, 4) -> (N, H/2, W/2, 4): the 2 x 2 mean, rounded once; channel 3 is 0."""
+    n, h, w = _swd_phys(x, "swd_pool")
+    out = torch.empty((n, h // 2, w // 2, 4), dtype=torch.float32, device=x.device)
+    _call("vcg_swd_pool", _ptr(x), _ptr(out), n, h, w, _stream())
+    return out
+
+
+def swd_pool_adjoint_add(coarse, fine):
+    """fine (N, H, W, 4) += coarse (N, H/2, W/2, 4) / 4, in place: the adjoint of `swd_pool` added into the finer gradient map."""
+    n, h, w = _swd_phys(fine, "swd_pool_adjoint_add")
+    nc, hc, wc = _swd_phys(coarse, "swd_pool_adjoint_add")
+    if (n, h, w) != (nc, 2 * hc, 2 * wc):
+        raise RuntimeError(f"swd_pool_adjoint_add: coarse {tuple(coarse.shape)} is not the half-size map of fine {tuple(fine.shape)}")
+    _call("vcg_swd_pool_adjoint_add", _ptr(coarse), _ptr(fine), n, h, w, _stream())
+    return fine
+
+
+def swd_grid_gather(level, s, oy, ox):
+    """The 7x7x3 patch at in-cell offset (oy, ox) of every s x s cell of the physical (N, H, W, 4) `level` -> (n, 147), row
+    (image, cell row, cell column), a patch flattened as (c, dy, dx)."""
+    n, h, w = _swd_phys(level, "swd_grid_gather")
+    s, oy, ox = (_swd_int(v, k, "swd_grid_gather") for k, v in (("s", s), ("oy", oy), ("ox", ox)))
+    rows = n * (h // s) * (w // s) if s > 0 else 0
+    out = torch.empty((max(rows, 1), SWD_DESC), dtype=torch.float32, device=level.device)
+    _call("vcg_swd_grid_gather", _ptr(level), _ptr(out), n, h, w, s, oy, ox, _stream())
+    return out
+
+
+def swd_grid_scatter(gdesc, shape, s, oy, ox, scale=1.0, g=None):
+    """The adjoint of `swd_grid_gather` on a level of `shape` = (N, H, W): a fresh physical (N, H, W, 4) map holding every element
+    of gdesc (n, 147), times `scale` and the device scalar `g` if given, at its pixel, and +0 everywhere else."""
+    _require_gpu(gdesc, "swd_grid_scatter")
+    n, h, w = (_swd_int(v, "shape", "swd_grid_scatter") for v in shape)
+    s, oy, ox = (_swd_int(v, k, "swd_grid_scatter") for k, v in (("s", s), ("oy", oy), ("ox", ox)))
+    rows = n * (h // s) * (w // s) if s > 0 else 0
+    if gdesc.dim() != 2 or not gdesc.is_contiguous() or (rows > 0 and tuple(gdesc.shape) != (rows, SWD_DESC)):
+        raise RuntimeError(f"swd_grid_scatter: gdesc must be a contiguous ({rows}, {SWD_DESC}) matrix, got shape {tuple(gdesc.shape)}")
+    if g is not None:
+        _require_gpu(g, "swd_grid_scatter")
+        if g.numel() != 1:
+            raise RuntimeError(f"swd_grid_scatter: g must hold one value, got shape {tuple(g.shape)}")
+    out = torch.empty((max(n, 1), max(h, 1), max(w, 1), 4), dtype=torch.float32, device=gdesc.device)
+    _call("vcg_swd_grid_scatter", _ptr(gdesc), _ptr(g), float(scale), _ptr(out), n, h, w, s, oy, ox, _stream())
+    return out
+
+
+def sort_columns_indexed(x):
+    """`sort_columns` that remembers where each key came from: (keys, rows), both with x's layout, rows int32; ordered by
+    (key, row), which is what a stable argsort gives.  n <= 8192."""
+    _require_gpu(x, "sort_columns_indexed")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise RuntimeError(f"sort_columns_indexed: expected an (n, cols) matrix, got shape {tuple(x.shape)}")
+    n, cols = x.shape
+    if n > SWD_LOSS_MAX_DESC:
+        raise RuntimeError(f"sort_columns_indexed: {n} rows exceed {SWD_LOSS_MAX_DESC}: a column's keys and rows are sorted in 64 KiB of LDS")
+    if x.is_contiguous():
+        rs, cs = cols, 1
+    elif x.t().is_contiguous():
+        rs, cs = 1, n
+    else:
+        raise RuntimeError("sort_columns_indexed: the matrix must be contiguous or the transpose of a contiguous one")
+    keys = torch.empty_like(x.t()).t() if rs == 1 else torch.empty_like(x)
+    rows = torch.empty(keys.t().shape if rs == 1 else keys.shape, dtype=torch.int32, device=x.device)
+    rows = rows.t() if rs == 1 else rows
+    _call("vcg_sort_columns_indexed", _ptr(x), _ptr(keys), _ptr(rows), n, cols, rs, cs, _stream())
+    return keys, rows
+
+
+def swd_pair_loss(a_sorted, b_sorted, perm_a, weight=1.0, total=None):
+    """One level's value and signed gradient from the sorted projections, (n, D) views with strides (1, n) as `swd_project`
+    and the sorts hand them over: -> (out, gproj, total).  total (one float64 on the device; None: a fresh one, started at 0)
+    += weight * mean |a_sorted - b_sorted|, out = float32(total) as a 0-dim tensor, gproj (D, n) contiguous with
+    gproj[d][perm_a[i][d]] = sign(a_sorted[i][d] - b_sorted[i][d]), not scaled."""
+    _require_gpu(a_sorted, "swd_pair_loss")
+    _require_gpu(b_sorted, "swd_pair_loss")
+    if a_sorted.dim() != 2 or a_sorted.numel() == 0 or not a_sorted.t().is_contiguous():
+        raise RuntimeError(f"swd_pair_loss: expected (n, D) projections with strides (1, n), got shape {tuple(a_sorted.shape)} "
+                           f"strides {a_sorted.stride()}")
+    for t, name in ((b_sorted, "b_sorted"), (perm_a, "perm_a")):
+        if t.shape != a_sorted.shape or t.stride() != a_sorted.stride() or t.device != a_sorted.device:
+            raise RuntimeError(f"swd_pair_loss: {name} {tuple(t.shape)} {t.stride()} does not match a_sorted {tuple(a_sorted.shape)} "
+                               f"{a_sorted.stride()}")
+    if perm_a.dtype != torch.int32:
+        raise RuntimeError(f"swd_pair_loss: perm_a must be int32, got {perm_a.dtype}")
+    n, d = a_sorted.shape
+    accumulate = total is not None
+    if accumulate and (total.dtype != torch.float64 or total.numel() != 1 or total.device != a_sorted.device):
+        raise RuntimeError("swd_pair_loss: total must be one float64 value on the projections' device")
+    if not accumulate:
+        total = torch.empty(1, dtype=torch.float64, device=a_sorted.device)
+    ws = torch.empty(_scratch("vcg_swd_pair_loss_workspace", n, d) // 4, dtype=torch.float32, device=a_sorted.device)
+    gproj = torch.empty((d, n), dtype=torch.float32, device=a_sorted.device)
+    out = torch.empty((), dtype=torch.float32, device=a_sorted.device)
+    _call("vcg_swd_pair_loss", _ptr(a_sorted), _ptr(b_sorted), _ptr(perm_a), _ptr(gproj), n, d, float(weight), int(accumulate),
+          _ptr(total), _ptr(out), _ptr(ws), ws.numel() * 4, _stream())
+    return out, gproj, total
+
+
+def swd_unit_columns(x):
+    """A contiguous (K, D) matrix with every column scaled to unit 2-norm (the sum of squares in double)."""
+    _require_gpu(x, "swd_unit_columns")
+    if x.dim() != 2 or not x.is_contiguous() or x.numel() == 0:
+        raise RuntimeError(f"swd_unit_columns: expected a contiguous (K, D) matrix, got shape {tuple(x.shape)}")
+    out = torch.empty_like(x)
+    _call("vcg_swd_unit_columns", _ptr(x), _ptr(out), x.shape[0], x.shape[1], _stream())
+    return out
+
+
+def swd_loss_geometry(n_images, h, w, levels):
+    """[(H_k, W_k, s_k, n_k)] of the `levels` levels of the loss on `n_images` H x W images; refuses more levels than the image has."""
+    levels = _swd_int(levels, "levels", "swd_loss")
+    if not 1 <= levels <= SWD_LOSS_MAX_LEVELS:
+        raise RuntimeError(f"swd_loss: levels must be an integer in 1..{SWD_LOSS_MAX_LEVELS}, got {levels}")
+    have = swd_loss_levels(h, w)
+    if levels > have:
+        raise RuntimeError(f"swd_loss: {levels} levels asked of {h}x{w} images, which have {have} (a level's sides are even halves "
+                           "of at least 16)")
+    out = []
+    for k in range(levels):
+        hk, wk = h >> k, w >> k
+        s = swd_cell_side(n_images, hk, wk)
+        out.append((hk, wk, s, n_images * (hk // s) * (wk // s)))
+    return out
+
+
+class _SwdLossFn(torch.autograd.Function):
+    """The stage calls of `swd_loss` chained.  Kept for the backward: gproj (D, n_k) per level, the directions and the geometry —
+    no image."""
+
+    @staticmethod
+    def forward(ctx, a, b, levels, offsets, dirs):
+        la, lb = as_phys(a), as_phys(b)
+        n_img, h, w = la.shape[:3]
+        geom, kept, out, total = [], [], None, None
+        for k, (hk, wk, s, n) in enumerate(swd_loss_geometry(n_img, h, w, levels)):
+            if k:
+                la, lb = swd_pool(la), swd_pool(lb)
+            oy, ox = offsets[k]
+            pa = swd_project(swd_grid_gather(la, s, oy, ox), dirs)
+            pb = swd_project(swd_grid_gather(lb, s, oy, ox), dirs)
+            ka, ra = sort_columns_indexed(pa)
+            out, gproj, total = swd_pair_loss(ka, sort_columns(pb), ra, 1.0 / levels, total)
+            kept.append(gproj)
+            geom.append((hk, wk, s, int(oy), int(ox), n))
+        ctx.save_for_backward(dirs, *kept)
+        ctx.geom = (n_img, levels, tuple(geom))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        n_img, levels, geom = ctx.geom
+        dirs, *kept = ctx.saved_tensors
+        g = g.contiguous()
+        coarser = None
+        for (hk, wk, s, oy, ox, n), gproj in zip(reversed(geom), reversed(kept)):
+            gdesc = swd_project(dirs, gproj).t()          # (n, 147): the projection with the roles swapped
+            ga = swd_grid_scatter(gdesc, (n_img, hk, wk), s, oy, ox, 1.0 / (n * dirs.shape[1] * levels), g)
+            if coarser is not None:
+                swd_pool_adjoint_add(coarser, ga)
+            coarser = ga
+        return logical_of(coarser, 3), None, None, None, None
+
+
+def swd_loss(generated, target, levels, plan):
+    """Sliced Wasserstein distance between the 7x7x3 patch sets of `generated` and `target`, (N, 3, H, W) images with H, W >= 16,
+    over `levels` in 1..3 levels of a 2 x 2 box pyramid: per level one patch per s x s cell at the plan's offset, projected on
+    the plan's 128 unit directions, every direction sorted, mean |sorted generated - sorted target|; the mean over the levels,
+    a 0-dim fp32 tensor.  `plan`: SwdPlan.  `target` takes no gradient."""
+    if target.requires_grad:
+        raise RuntimeError("swd_loss: the target must not require a gradient (only d loss / d generated is computed)")
+    if generated.shape != target.shape:
+        raise RuntimeError(f"swd_loss: shape mismatch {tuple(generated.shape)} vs {tuple(target.shape)}")
+    if generated.dim() != 4 or generated.shape[1] != 3:
+        raise RuntimeError(f"swd_loss: expected (N, 3, H, W) images, got shape {tuple(generated.shape)}")
+    _require_gpu(generated, "swd_loss")
+    _require_gpu(target, "swd_loss")
+    geom = swd_loss_geometry(generated.shape[0], generated.shape[2], generated.shape[3], levels)
+    offsets, dirs = plan
+    _require_gpu(dirs, "swd_loss")
+    if tuple(dirs.shape) != (SWD_DESC, SWD_LOSS_DIRS) or not dirs.is_contiguous() or dirs.requires_grad:
+        raise RuntimeError(f"swd_loss: the plan's directions must be a contiguous ({SWD_DESC}, {SWD_LOSS_DIRS}) matrix without a "
+                           f"gradient, got shape {tuple(dirs.shape)}")
+    if len(offsets) != len(geom):
+        raise RuntimeError(f"swd_loss: the plan holds {len(offsets)} offsets for {len(geom)} levels")
+    offsets = tuple((_swd_int(oy, "oy", "swd_loss"), _swd_int(ox, "ox", "swd_loss")) for oy, ox in offsets)
+    for (oy, ox), (_, _, s, _) in zip(offsets, geom):
+        if not (0 <= oy <= s - SWD_PATCH and 0 <= ox <= s - SWD_PATCH):
+            raise RuntimeError(f"swd_loss: offset ({oy}, {ox}) outside [0, {s - SWD_PATCH}] of a {s}x{s} cell")
+    return _SwdLossFn.apply(generated, target, int(levels), offsets, dirs)

@@ -44,7 +44,8 @@ REFERENCE_ARCHS = ["autoencoder", "doubleae", "doublevae", "vae", "aegan", "vaeg
                    "cycleaegan", "cyclevaegan"]
 BUILT = tuple(REFERENCE_ARCHS)
 SSIM_ARCHS = ("autoencoder", "vae", "cycleaegan", "cyclevaegan")     # the models whose configure_loss takes Losses.IMAGE_TERMS (named for the first)
-IMAGE_TERM_HELP = {                    # --lambda_<key>, per row of Losses.IMAGE_TERMS
+SWD_ARCHS = ("cycleae", "cyclevae", "cycleaegan", "cyclevaegan")       # the models whose configure_loss builds the sliced Wasserstein term
+IMAGE_TERM_HELP = {                  # --lambda_<key>, per row of Losses.IMAGE_TERMS
     "ssim": "weight of the structural term 1 - SSIM",
     "grad": "weight of the multi-scale gradient-matching term (an L1 on the finite differences of generated - target)",
     "freq": "weight of the focal frequency term (the weighted squared distance between the 2-D spectra of generated and target)",
@@ -269,6 +270,12 @@ def build_parser():
                    help="number of scales of the gradient-matching term; scale s keeps every 2^s-th pixel")
     p.add_argument("--freq_alpha", type=_nonneg("--freq_alpha", ""), default=1.0,
                    help="exponent of the focal frequency term's spectrum weight |difference|^alpha; 0: an unweighted spectral MSE")
+    p.add_argument("--lambda_swd", type=_nonneg("--lambda_swd", " (0: the term is not computed)"), default=0.0,
+                   help="weight of the sliced Wasserstein term swd(G(x), y) + swd(F(y), x): a distance between the patch "
+                        "distributions of the translated batch and of the other domain's batch, which needs no pairing and no "
+                        "discriminator (" + ", ".join(SWD_ARCHS) + "); 0: not computed")
+    p.add_argument("--swd_levels", type=int, default=3, choices=(1, 2, 3),
+                   help="levels of the sliced Wasserstein term's 2x2 box pyramid (a level needs sides of at least 16)")
     p.add_argument("--clip_grad_norm", type=clip_bound, default=0.0,
                    help="clip each optimizer's gradient to this global 2-norm inside the fused Adam step (every architecture); "
                         "a step whose gradient holds a NaN / Inf is skipped; 0: off")
@@ -366,6 +373,15 @@ def main(args):
         raise ValueError(f"--grad_scales must be 1, 2, 3 or 4, got {image_kw['grad_scales']}")
     if not math.isfinite(image_kw["freq_alpha"]) or image_kw["freq_alpha"] < 0.0:
         raise ValueError(f"--freq_alpha must be finite and >= 0, got {image_kw['freq_alpha']}")
+    lambda_swd = image_kw["lambda_swd"] = getattr(args, "lambda_swd", 0.0)
+    if not math.isfinite(lambda_swd) or lambda_swd < 0.0:
+        raise ValueError(f"--lambda_swd must be finite and >= 0 (0: the term is not computed), got {lambda_swd}")
+    if lambda_swd != 0.0 and args.architecture not in SWD_ARCHS:
+        raise ValueError(f"--lambda_swd is supported by {', '.join(SWD_ARCHS)} only, not by {args.architecture}: "
+                         "the flag would be ignored")
+    image_kw["swd_levels"] = getattr(args, "swd_levels", 3)
+    if image_kw["swd_levels"] not in (1, 2, 3):
+        raise ValueError(f"--swd_levels must be 1, 2 or 3, got {image_kw['swd_levels']}")
     clip = getattr(args, "clip_grad_norm", 0.0)
     if not math.isfinite(clip) or clip < 0.0:
         raise ValueError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {clip}")
@@ -433,7 +449,8 @@ def main(args):
     if ema_decay > 0.0 and rank == 0:
         print(f"Averaged generator weights (decay {ema_decay}): the test loss, and with it best_model.pth, is the averaged weights'")
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
-                         lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon, **image_kw)
+                         lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
+                         swd_seed=ops.rank_seed(args.seed, rank) % 2 ** 32, **image_kw)      # plans per rank, as the eps streams
     if world > 1:
         parallel.attach(model)
     same_xy = args.architecture in ("autoencoder", "vae")

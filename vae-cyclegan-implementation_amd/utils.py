@@ -70,7 +70,11 @@ def save_checkpoint(model, epoch, loss, args, filename, best_test_loss=None, poo
     {discriminator name: ImagePool.state_dict()}: count, image shape, the plan generator's state and the stored images, so that
     a resumed run shows its discriminators what the uninterrupted run would have.  `pool_images=False` leaves the key out
     (best_model.pth: a file to evaluate, not to resume).  With more than one rank every rank owns different pools and one rank
-    writes the file: the key is left out, and a resumed run starts with empty pools on every rank."""
+    writes the file: the key is left out, and a resumed run starts with empty pools on every rank.
+
+    A model with the sliced Wasserstein term (configure_loss(lambda_swd=...)) adds `vcg_swd_loss` = the loss object's state_dict():
+    its seed and the counter its plans are drawn from, so that a resumed run continues the sequence of offsets and directions
+    (with more than one rank every rank keeps its own seed and takes the counter, which is the same on all of them)."""
     rank = _rank()
     seed = int(ops._RNG["seed"])
     checkpoint = {
@@ -90,6 +94,8 @@ def save_checkpoint(model, epoch, loss, args, filename, best_test_loss=None, poo
             _tell_pools_are_per_rank()
         else:
             checkpoint["vcg_image_pool"] = model.save_pool_state()
+    if getattr(model, "swd_enabled", False):
+        checkpoint["vcg_swd_loss"] = model.save_swd_state()
     torch.save(checkpoint, filename)
     print(f"Checkpoint saved to {filename}")
 
@@ -131,6 +137,14 @@ def load_checkpoint(model, filename, device):
             model.load_pool_state(checkpoint["vcg_image_pool"], device=device)
         else:
             print(f"{filename} holds no image history pools: they start empty")
+    if getattr(model, "swd_enabled", False):             # (a `vcg_swd_loss` key in the file of a run without the term is ignored)
+        if "vcg_swd_loss" in checkpoint:
+            seed = model.swd_term[1].seed                # this rank's (train.py derives it per rank; one rank wrote the file)
+            model.load_swd_state(checkpoint["vcg_swd_loss"])
+            if _world() > 1:
+                model.swd_term[1].seed = seed
+        else:
+            print(f"{filename} holds no sliced Wasserstein plan counter: the plans start from step 0")
     ops.PARAM_EPOCH[0] += 1                              # load_state_dict wrote through .data: drop every weight pack
     epoch, loss = checkpoint["epoch"], checkpoint["loss"]
     print(f"Loaded checkpoint from {filename} (epoch {epoch}, loss {loss:.4f})")
