@@ -31,10 +31,10 @@ def _act(t, a):
             ops.ACT_SIGMOID: torch.sigmoid}[a](t)
 
 
-def torch_block(x, w, b, res, stride, pad, ups, epi, norm, post, shuffle):
+def torch_block(x, w, b, res, stride, pad, ups, epi, norm, post, shuffle, reflect=True):
     if ups == 2:
         x = F.pixel_unshuffle(x, 2)
-    t = F.conv2d(F.pad(x, (pad,) * 4, mode="reflect"), w, b, stride=stride)
+    t = F.conv2d(F.pad(x, (pad,) * 4, mode="reflect" if reflect else "constant"), w, b, stride=stride)
     t = _act(t, epi)
     if norm:
         t = _act(F.instance_norm(t, eps=1e-5), post)

@@ -75,7 +75,7 @@ class ImagePool:
         """The contiguous buffer behind `fake` and how to view the result: the discriminators read pitch-4 NHWC images
         (ops.as_phys aliases them), anything else is taken as it lies."""
         from . import ops
-        if fake.dim() == 4 and ops.is_nhwc_view(fake):
+        if ops.can_alias(fake):
             return ops.phys_of(fake), fake.shape[1]
         return fake.contiguous(), None
 

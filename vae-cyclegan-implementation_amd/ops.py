@@ -2,7 +2,8 @@
 
 Tensors keep the reference's LOGICAL shape (N, C, H, W) but live in HBM as NHWC with a
 channel pitch that is a multiple of 4 (`nhwc_view`), so every module boundary of
-Networks.py is a zero-copy hand-off.  torch is used for device memory, streams and the
+Networks.py is a zero-copy hand-off.  Which tensors are read in place is `can_alias`'s decision; `logical_of` is how a buffer
+is declared to be the package's own (pad lanes zero) — read its contract before calling it on a buffer of yours.  torch is used for device memory, streams and the
 autograd graph only; every arithmetic op below is a HIP kernel.  There is no fallback:
 CPU tensors raise.
 """
@@ -205,19 +206,68 @@ def nhwc_strides(n, c, h, w):
 
 
 def is_nhwc_view(t):
+    """Do the STRIDES of t say NHWC at the channel pitch?  Strides alone do not make t the package's storage: `can_alias` decides."""
     n, c, h, w = t.shape
     return t.stride() == nhwc_strides(n, c, h, w)
 
 
+def _own_pad_lanes(storage, c=None):
+    """The mark on a storage whose pad lanes (channels c .. pitch(c) - 1 of every pixel) are the package's own: written as zeros
+    by the kernel that filled it, or never read as data.  `c` given: leave the mark (`logical_of`); -> the marked channel count.
+    It sits on the storage, not on a tensor object, so a detach(), a batch slice or a saved tensor of the view keeps it, and
+    whatever torch allocates itself (a sum of two gradients, a clone, a slice of somebody's RGBA image) never has it."""
+    if c is not None:
+        storage._vcg_pad_c = c
+    return getattr(storage, "_vcg_pad_c", None)
+
+
+def can_alias(t):
+    """May the kernels read logical (N, C, H, W) `t` in place as the physical (N, H, W, pitch(C)) buffer `phys_of` describes?  The
+    one decision behind `as_phys`, `to_nhwc` and `to_nchw_contiguous`; pure host logic, any device.  All of:
+      * the strides are the NHWC strides at the channel pitch (size-1 dimensions included: torch may give those other strides,
+        and such a tensor takes the copy);
+      * the alias starts on a 16-byte boundary (the kernels load float4) and its N * H * W * pitch floats end inside the storage
+        (a channel slice x4[:, 1:4] of an RGBA image has the right strides and would end one float past it);
+      * there are no pad lanes (pitch(C) == C), or they are known to be the package's own zeros: the storage carries the mark
+        `logical_of` leaves, for this C.  x4[:, :3] has the strides of a pitch-4 RGB image with alpha in the pad lane, which
+        the reductions (L1, InstanceNorm statistics, operand maxima) would take for data: it is copied, never aliased."""
+    if t.dim() != 4:
+        return False
+    n, c, h, w = t.shape                      # (written out flat: this runs for every operand of every Function of a step)
+    p = (c + 3) // 4 * 4
+    hwp = h * w * p
+    if t.stride() != (hwp, 1, w * p, p):
+        return False
+    off = t.storage_offset()
+    if off % 4 or t.data_ptr() % 16:
+        return False
+    st = t.untyped_storage()
+    if (off + n * hwp) * t.element_size() > st.nbytes():
+        return False
+    return p == c or getattr(st, "_vcg_pad_c", None) == c
+
+
 def phys_of(t):
-    """(N,H,W,P) contiguous alias of a logical (N,C,H,W) nhwc view."""
+    """(N,H,W,P) contiguous alias of a logical (N,C,H,W) nhwc view (one `can_alias` admits)."""
     n, c, h, w = t.shape
     p = pitch(c)
     return t.as_strided((n, h, w, p), (h * w * p, w * p, p, 1), t.storage_offset())
 
 
 def logical_of(phys, c):
+    """The logical (N, c, H, W) view of the physical (N, H, W, P) buffer `phys`.
+
+    CONTRACT: calling it DECLARES the buffer to be in the package's layout.  Where P != c the caller vouches that the pad lanes
+    c .. P - 1 of every pixel are zeros by the time a kernel reads the view, or that only kernels that never look at them will
+    (the running statistics of translate.py, which `vcg_sample_accumulate` writes whole; the fake tensors of custom_ops).  The
+    storage is marked with c (`_own_pad_lanes`), and `can_alias` then hands the buffer to the kernels in place — the reductions
+    (L1, InstanceNorm statistics, operand maxima) run over the whole pitch and take whatever the pad lanes hold for data.
+    One mark per storage: viewing one storage at two different c sends the earlier view down the (correct, slower) copy path.
+    The mark is a Python attribute of the storage object, which torch keeps alive with the storage; a storage that arrives
+    without it (pickled, deep-copied) is simply copied."""
     n, h, w, p = phys.shape
+    if p != c:
+        _own_pad_lanes(phys.untyped_storage(), c)
     return phys.as_strided((n, c, h, w), (h * w * p, 1, w * p, p), phys.storage_offset())
 
 
@@ -237,7 +287,7 @@ def as_phys(t):
     if t.dim() != 4:
         raise RuntimeError(f"expected a 4-D (N,C,H,W) tensor, got shape {tuple(t.shape)}")
     _require_gpu(t, "as_phys")
-    if is_nhwc_view(t):
+    if can_alias(t):
         return phys_of(t)
     return _to_phys_copy(t)
 
@@ -245,7 +295,7 @@ def as_phys(t):
 def to_nchw_contiguous(t):
     """Logical (N,C,H,W) nhwc view -> plain contiguous NCHW copy."""
     _require_gpu(t, "to_nchw")
-    if not is_nhwc_view(t):
+    if not can_alias(t):
         return t.contiguous()
     n, c, h, w = t.shape
     ph = phys_of(t)
@@ -266,7 +316,7 @@ class _ToNHWC(torch.autograd.Function):
 
 def to_nhwc(x):
     """x.to(channels-last) with pitch-4 images; differentiable; no-op when already laid out."""
-    if x.dim() == 4 and x.is_cuda and is_nhwc_view(x):
+    if x.is_cuda and can_alias(x):
         return x
     _require_gpu(x, "to_nhwc")
     return _ToNHWC.apply(x)
@@ -308,6 +358,11 @@ class ConvSpec:
         self.cin, self.cout, self.k = cin, cout, k          # logical channels of the torch conv
         self.stride, self.pad, self.reflect, self.ups = stride, pad, reflect, ups
         self.epi_act, self.norm, self.post_act, self.shuffle = epi_act, norm, post_act, shuffle
+        if ACT_SIGMOID in (epi_act, post_act) and pitch(cout) != cout:
+            # the activation runs over the whole pitch and sigmoid(0) = 0.5: the pad lanes of the output would not be the zeros
+            # every consumer counts on (L1 over the physical buffer, operand maxima, InstanceNorm statistics)
+            raise RuntimeError(f"ConvSpec: a Sigmoid block needs a multiple of 4 output channels, got {cout}: sigmoid(0) = 0.5 "
+                               "would be written into the pad lanes of the output")
         if ups == 2:
             assert cin % 4 == 0
             self.cin_phys_log = cin // 4                   # channels of the un-shuffled input
@@ -728,7 +783,16 @@ class _ConvBlockFn(torch.autograd.Function):
         d_res = g if ctx.has_res else None
         wparam, bparam = ctx.wparam, ctx.bparam
         want_w = wparam is not None and wparam.requires_grad and id(wparam) not in _NO_WGRAD
-        want_b = want_w and bparam is not None and bparam.requires_grad
+        # A trainable bias under a frozen weight still gets its gradient: from the InstanceNorm backward where that takes it
+        # (`gb_here`), else from the weight gradient's own column sums, whose weight part then goes to scratch and is dropped.
+        bias_alone = (not want_w and wparam is not None and not wparam.requires_grad and bparam is not None
+                      and bparam.requires_grad and id(bparam) not in _NO_WGRAD)
+        want_b = (want_w or bias_alone) and bparam is not None and bparam.requires_grad
+        run_wgrad = want_w or (bias_alone and not spec.norm)
+        if run_wgrad and ctx.x_deferred and ctx.saved_state is None:
+            # refused before anything is accumulated: the InstanceNorm backward below already adds into the bias gradient
+            raise RuntimeError("the weight gradient of a layer that took a deferred-InstanceNorm input needs the forward's kept "
+                               "state (a second backward through the same graph)")
         # conv -> act -> InstanceNorm (D, U, R.conv1): the bias gradient is the column sum of dt, taken by the pass that writes
         # dt instead of a pass of its own inside the weight gradient (same box, 4 runs: 36.49 / 36.47 against 36.48 / 36.49 ms
         # per step — those column sums ran on the side stream —, -2 GB, -64 launches)
@@ -742,11 +806,13 @@ class _ConvBlockFn(torch.autograd.Function):
         # x as the forward saw it?  (autograd refuses a saved tensor that was modified in place, so this only guards a
         # handle that has aged out between forward and backward: measured again below by the library)
         x_amax = ctx.x_amax if (ctx.x_amax and ctx.x_key == (xp._version, xp.data_ptr()) and lib.vcg_amax_valid(ctx.x_amax)) else 0
-        if want_w:
+        if bias_alone and gb_here is not None and GRAD_READY_HOOK[0] is not None:
+            GRAD_READY_HOOK[0](None, bparam, torch.cuda.current_stream(dev))
+        if run_wgrad:
             # hand the 4x buffer back once the weight gradient has consumed it — not on a traversal that skips the weight
             # gradient (`no_wgrad`: the G phase through a discriminator), whose retained graph is differentiated again
             ctx.saved_state = None
-            gw = _grad_buffer(wparam)
+            gw = _grad_buffer(wparam) if want_w else torch.zeros_like(wparam, memory_format=torch.contiguous_format)
             gb = _grad_buffer(bparam) if want_b else None
             if spec.norm and spec.epi_act == ACT_NONE:
                 # InstanceNorm directly on conv + bias (CaSb, R.conv2): the mean subtraction cancels the bias, its gradient
@@ -755,9 +821,6 @@ class _ConvBlockFn(torch.autograd.Function):
                 gb = None
             if gb_here is not None:
                 gb = None            # already accumulated by block_dt above, on the main stream
-            if ctx.x_deferred and saved is None:
-                raise RuntimeError("the weight gradient of a layer that took a deferred-InstanceNorm input needs the forward's kept "
-                                   "state (a second backward through the same graph)")
             if _OVERLAP[0]:
                 side = _side_stream(dev)
                 side.wait_stream(torch.cuda.current_stream(dev))      # dt (and, the first time, x) are ready
@@ -767,6 +830,8 @@ class _ConvBlockFn(torch.autograd.Function):
                 dt.record_stream(side)
                 if saved is not None:
                     saved.record_stream(side)
+                if not want_w:
+                    gw.record_stream(side)
                 wstream = side
             else:
                 conv_wgrad(cd, xp, dt, gw, gb, saved, x_amax, dt_amax, ctx.flops, ctx.tag)
@@ -775,22 +840,34 @@ class _ConvBlockFn(torch.autograd.Function):
             if members is not None:
                 # a fused kernel (FusedConvPair): its gradient was accumulated into scratch; hand the slices to the members'
                 # own gradient buffers on the stream the weight gradient ran on, and report THEM to the data-parallel reducer
+                # A member that is frozen (or under `no_wgrad`) keeps its `.grad` as it is — None stays None: its slice of the
+                # scratch is cleared instead of handed over, so that nothing stale is added once it trains again.
+                live = []
                 with torch.cuda.stream(wstream):
                     for (mw, mb), (wlo, whi), (blo, bhi) in members:
-                        _native.check(lib.vcg_add_into(_ptr(_grad_buffer(mw)), ctypes.c_void_p(gw.data_ptr() + 4 * wlo), whi - wlo,
-                                                       _stream()), "vcg_add_into")
-                        if gb is not None and mb is not None:
-                            _native.check(lib.vcg_add_into(_ptr(_grad_buffer(mb)), ctypes.c_void_p(gb.data_ptr() + 4 * blo), bhi - blo,
-                                                           _stream()), "vcg_add_into")
+                        src_w = ctypes.c_void_p(gw.data_ptr() + 4 * wlo)
+                        src_b = ctypes.c_void_p(gb.data_ptr() + 4 * blo) if gb is not None and mb is not None else None
+                        take_w = mw.requires_grad and id(mw) not in _NO_WGRAD
+                        take_b = take_w and src_b is not None and mb.requires_grad
+                        if take_w:
+                            _native.check(lib.vcg_add_into(_ptr(_grad_buffer(mw)), src_w, whi - wlo, _stream()), "vcg_add_into")
+                        else:
+                            _native.check(lib.vcg_fill(src_w, 0.0, whi - wlo, _stream()), "vcg_fill")
+                        if take_b:
+                            _native.check(lib.vcg_add_into(_ptr(_grad_buffer(mb)), src_b, bhi - blo, _stream()), "vcg_add_into")
+                        elif src_b is not None:
+                            _native.check(lib.vcg_fill(src_b, 0.0, bhi - blo, _stream()), "vcg_fill")
+                        if take_w:
+                            live.append((mw, mb if take_b else None))
                 if GRAD_READY_HOOK[0] is not None:
-                    for (mw, mb), _, _ in members:
+                    for mw, mb in live:
                         GRAD_READY_HOOK[0](mw, mb, wstream)
             elif GRAD_READY_HOOK[0] is not None:
                 if gb_here is not None:      # the bias gradient came from the main stream, the weight gradient from `wstream`
                     GRAD_READY_HOOK[0](None, bparam, torch.cuda.current_stream(dev))
                     GRAD_READY_HOOK[0](wparam, None, wstream)
                 else:
-                    GRAD_READY_HOOK[0](wparam, bparam, wstream)
+                    GRAD_READY_HOOK[0](wparam if want_w else None, bparam, wstream)
         dx = None
         if ctx.needs_input_grad[0] and id(spec) not in _NO_DGRAD:
             dx = logical_of(conv_dgrad(cd, dt, wf, dt_amax, ctx.flops, ctx.tag), spec.cin_phys_log)
@@ -817,6 +894,11 @@ class FusedConvPair:
     members' own gradients (`_ConvBlockFn.backward`, `_vcg_members`)."""
 
     def __init__(self, conv_a, conv_b, spec):
+        ca, cb = conv_a.weight.shape[0], conv_b.weight.shape[0]
+        if ca % 4 or cb % 4:
+            # the split, its adjoint and the hand-over of the gradient slices move float4s (vcg_chan_split, vcg_add_into)
+            raise RuntimeError(f"FusedConvPair: both members need a multiple of 4 output channels, got {ca} and {cb}; "
+                               "run the two convolutions separately")
         self.a, self.b, self.spec = conv_a, conv_b, spec
         self.w = self.bias = None
         self.key = None
@@ -1290,7 +1372,18 @@ class _KLFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, lv):
         lib = _native.lib()
-        mup, lvp, _ = _pair_phys(mu, lv)
+        # vcg_kl_fwd / vcg_kl_bwd take the mean over the n values they are handed: the physical buffers serve only where they hold
+        # nothing but the logical values.  A latent with pad lanes (latent_dim % 4 != 0: 6 lives at pitch 8) goes in as a dense
+        # copy — over the physical buffer the sum is the same (a pad lane adds 1 + 0 - 0 - e^0 = 0) but the mean is 6/8 of it.
+        ctx.phys = mu.dim() == 4 and pitch(mu.shape[1]) == mu.shape[1]
+        if ctx.phys:
+            mup, lvp, _ = _pair_phys(mu, lv)
+        else:
+            if mu.shape != lv.shape:
+                raise RuntimeError(f"shape mismatch {tuple(mu.shape)} vs {tuple(lv.shape)}")
+            _require_gpu(mu, "loss")
+            _require_gpu(lv, "loss")
+            mup, lvp = mu.contiguous(), lv.contiguous()
         out = torch.empty((), dtype=torch.float32, device=mu.device)
         ws = workspace(lib.vcg_reduce_workspace(mup.numel()), mu.device)
         _native.check(lib.vcg_kl_fwd(_ptr(mup), _ptr(lvp), _ptr(out), mup.numel(), _ptr(ws), ws.numel() * 4, _stream()), "vcg_kl_fwd")
@@ -1306,7 +1399,7 @@ class _KLFn(torch.autograd.Function):
         gmu = torch.empty_like(mup)
         glv = torch.empty_like(lvp)
         _native.check(lib.vcg_kl_bwd(_ptr(mup), _ptr(lvp), _ptr(g), _ptr(gmu), _ptr(glv), mup.numel(), _stream()), "vcg_kl_bwd")
-        if len(ctx.shape) == 4:
+        if ctx.phys:
             return logical_of(gmu, ctx.shape[1]), logical_of(glv, ctx.shape[1])
         return gmu.view(ctx.shape), glv.view(ctx.shape)
 
@@ -1386,14 +1479,18 @@ class _FullMapSNFn(torch.autograd.Function):
         g = g.contiguous()
         dev = g.device
         wparam, bparam = ctx.wparam, ctx.bparam
-        if wparam is not None and wparam.requires_grad and id(wparam) not in _NO_WGRAD:
-            gw = _grad_buffer(wparam)
+        want_w = wparam is not None and wparam.requires_grad and id(wparam) not in _NO_WGRAD
+        # a trainable bias under a frozen weight: the same kernel, its weight part into scratch that is dropped
+        bias_alone = (not want_w and wparam is not None and not wparam.requires_grad and bparam is not None
+                      and bparam.requires_grad and id(bparam) not in _NO_WGRAD)
+        if want_w or bias_alone:
+            gw = _grad_buffer(wparam) if want_w else torch.zeros_like(wparam, memory_format=torch.contiguous_format)
             gb = _grad_buffer(bparam) if (bparam is not None and bparam.requires_grad) else None
             ws = workspace((k + 256) * 4, dev)
             _native.check(lib.vcg_fullmap_wgrad(_ptr(g), _ptr(xp), _ptr(wsn), _ptr(sigma), _ptr(u), _ptr(v), _ptr(gw),
                                                 _ptr(gb), n, c, kh, kw, _ptr(ws), ws.numel() * 4, _stream()), "vcg_fullmap_wgrad")
             if GRAD_READY_HOOK[0] is not None:
-                GRAD_READY_HOOK[0](wparam, bparam, torch.cuda.current_stream(dev))
+                GRAD_READY_HOOK[0](wparam if want_w else None, bparam, torch.cuda.current_stream(dev))
         dx = None
         if ctx.needs_input_grad[0]:
             dxp = torch.empty_like(xp)
@@ -1684,7 +1781,7 @@ def sample_accumulate(y, mean, m2, samples_in_chunk, seen):
     k = int(samples_in_chunk)
     for t, name in ((mean, "mean"), (m2, "m2")):
         _require_gpu(t, "sample_accumulate")
-        if t.dim() != 4 or t.shape[1] != 3 or not is_nhwc_view(t):
+        if t.dim() != 4 or t.shape[1] != 3 or not can_alias(t):
             raise RuntimeError(f"sample_accumulate: {name} must be a logical (N, 3, Hp, Wp) nhwc view, got shape {tuple(t.shape)}")
     n, _, hp, wp = mean.shape
     if mean.shape != m2.shape or k < 1 or tuple(y.shape) != (n * k, 3, hp, wp):
