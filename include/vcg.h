@@ -260,6 +260,30 @@ int vcg_ssim_loss_fwd(const float* a, const float* b, float* out, int N, int H, 
    positions.  The coefficients are recomputed from a and b (a 20-pixel halo per 16 x 16 pixel tile): no workspace.  There is
    no gradient with respect to b. */
 int vcg_ssim_loss_bwd(const float* a, const float* b, const float* gout, float* ga, int N, int H, int W, void* stream);
+/* Multi-scale structural loss (new: the reference has no such term): MS-SSIM (Wang, Simoncelli & Bovik 2003) over K = `scales`
+   in 1..5 levels of a 2 x 2 mean pyramid, H_{j+1} = H_j / 2, W_{j+1} = W_j / 2 (a last odd row or column is dropped), level 0 the
+   images; window, constants, layout and alignment of vcg_ssim_loss_fwd; min(H, W) >> (K - 1) >= 11 (the refusal names the largest
+   K the size allows).  Per level, image n and channel c, over the level's valid positions:
+     f_j = mean((2 s_ab + C2) / (s_a^2 + s_b^2 + C2)) for j < K - 1 (contrast-structure),   f_{K-1} = mean(S) (the full SSIM),
+     MS(n, c) = prod_j max(f_j, 1e-4)^{w_j},  w = the first K of (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) over their sum,
+     out[0] = 1 - mean over (n, c) of MS.
+   K = 1 is the structural loss wherever every per-channel mean is above 1e-4.  ws: vcg_msssim_loss_workspace(N, H, W, scales)
+   bytes (0 and vcg_last_error for bad arguments), 16-byte aligned: the pooled levels of a and b, one gradient map per pooled
+   level, the per-(n, c, tile) slots of every level, the factors f and the table coef[n][c][j] = d out / d f_j (0 where f_j was
+   clamped: a clamped factor passes no gradient, as torch.clamp).  Slots summed in a fixed order, no float atomics: the same
+   input gives the same bits.  csrc/msssim_loss.hip. */
+size_t vcg_msssim_loss_workspace(int N, int H, int W, int scales);
+/* new: the reference has no such term.  The forward defined above; it leaves in ws what vcg_msssim_loss_bwd reads. */
+int vcg_msssim_loss_fwd(const float* a, const float* b, float* out, int N, int H, int W, int scales, void* ws, size_t ws_bytes,
+                        void* stream);
+/* new: the reference has no such term.  ga = gout[0] * d out / d a, (N, H, W, 4) with channel 3 = 0, written for every pixel;
+   gout is read on the device.  ws: the workspace the forward of the SAME a, b, scales left (its pooled levels and coef are read,
+   its gradient maps written).  Coarse to fine, one launch per level: vcg_ssim_loss_bwd's recomputation with the level's
+   coefficients (of the contrast-structure part alone for j < K - 1) scaled by gout coef[n][c][j] / positions_j, plus the pooling
+   adjoint: pixel (y, x) with y < 2 H_{j+1}, x < 2 W_{j+1} receives 1/4 of level j + 1's gradient at (y / 2, x / 2).  There is no
+   gradient with respect to b. */
+int vcg_msssim_loss_bwd(const float* a, const float* b, const float* gout, float* ga, int N, int H, int W, int scales, void* ws,
+                        size_t ws_bytes, void* stream);
 /* Gradient-matching loss (new: the reference has no edge term): an L1 on the horizontal and vertical finite differences of
    d = a - b at S = `scales` in 1..4 subsampled scales (Eigen & Fergus 2015; Li & Snavely 2018).  With d_s[i, j] = d[i 2^s, j 2^s],
    H_s = ceil(H / 2^s), W_s = ceil(W / 2^s), s = 0 .. S - 1, and the sums taken over the N images and the 3 logical channels:

@@ -14,7 +14,12 @@ swd (the sliced Wasserstein term, DESIGN.md "Sliced Wasserstein training loss") 
 stage calls are timed one by one through ops on the level-0 tensors of the same batch, then ops.swd_loss (3 levels) forward and
 forward + backward, then the step with lambda_swd 0 and 1.
 
-    python tools/image_loss_bench.py <ssim|grad|freq|swd>        # STEP=0: kernels only
+msssim (5 scales; DESIGN.md "The multi-scale structural loss") is set against ssim on the same box: its pyramid holds 4/3 of
+level 0's pixels, so 4/3 of the structural loss's forward + backward plus the pooling traffic is the yardstick.  Its 2 x 2 pooling
+is a kernel of its own between the levels' forward launches; the extra line prices it by vcg_swd_pool, the same pooling of ONE
+image at level 0 (both images over all levels: about 2 x 4/3 of that), which is what fusing it into the forward could save.
+
+    python tools/image_loss_bench.py <ssim|msssim|grad|freq|swd>        # STEP=0: kernels only
 """
 import ctypes
 import importlib
@@ -33,7 +38,7 @@ dev = torch.device("cuda:0")
 HBM = 6.3e12          # practical bytes / s
 PEAK = 157.3e12       # fp32 MFMA, FLOP / s
 TILE, CHUNK = 64, 32  # csrc/freq_loss.hip: FF_TM = FF_TN, FF_TK
-SHAPES = {"ssim": [(8, 256, 256), (2, 32, 32)], "grad": [(8, 256, 256)], "freq": [(8, 256, 256)], "swd": [(8, 256, 256)]}
+SHAPES = {"ssim": [(8, 256, 256), (2, 32, 32)], "msssim": [(8, 256, 256)], "grad": [(8, 256, 256)], "freq": [(8, 256, 256)], "swd": [(8, 256, 256)]}
 ON_WEIGHT = {"swd": 1.0}          # the weight of the "on" step; 0.5 for the others
 lines = []
 
@@ -72,6 +77,12 @@ def term_calls(term, a, b, out, g, ga, n, h, w, st):
         return (lib.vcg_ssim_loss_workspace(n, h, w),
                 lambda ws: lib.vcg_ssim_loss_fwd(P(a), P(b), P(out), n, h, w, P(ws), ws.numel() * 4, st),
                 lambda ws: lib.vcg_ssim_loss_bwd(P(a), P(b), P(g), P(ga), n, h, w, st))
+    if term == "msssim":                                   # the backward reads what the forward left in the workspace
+        need = lib.vcg_msssim_loss_workspace(n, h, w, 5)   # ... so it is a buffer of the term's own, as in ops, not the shared one
+        keep = torch.empty(need // 4, dtype=torch.float32, device=dev)
+        return (need,
+                lambda ws: lib.vcg_msssim_loss_fwd(P(a), P(b), P(out), n, h, w, 5, P(keep), need, st),
+                lambda ws: lib.vcg_msssim_loss_bwd(P(a), P(b), P(g), P(ga), n, h, w, 5, P(keep), need, st))
     if term == "grad":
         return (lib.vcg_grad_loss_workspace(n, h, w, 4),
                 lambda ws: lib.vcg_grad_loss_fwd(P(a), P(b), P(out), n, h, w, 4, P(ws), ws.numel() * 4, st),
@@ -99,6 +110,8 @@ def kernels(term, n, h, w, rounds=15, warm=3):
         (f"vcg_{term}_loss_bwd", 3 * npx, lambda: bwd(ws)),
         ("vcg_l1_bwd (ga only)", 3 * npx, lambda: lib.vcg_l1_bwd(P(a), P(b), P(g), P(ga), None, a.numel(), n * 3 * h * w, st)),
     ]
+    if term == "msssim":
+        runs.insert(2, ("vcg_swd_pool (1 image)", npx + npx // 4, lambda: lib.vcg_swd_pool(P(a), P(ga), n, h, w, st)))
     for name, _, fn in runs:
         assert fn() == 0, lib.vcg_last_error()
     ts = {name: [] for name, _, _ in runs}
@@ -120,6 +133,9 @@ def kernels(term, n, h, w, rounds=15, warm=3):
         say(f"  {name:24s} {med[name]:10.2f} {min(ts[name]):8.2f} ..{max(ts[name]):7.2f} {tail}")
     new, l1 = med[f"vcg_{term}_loss_fwd"] + med[f"vcg_{term}_loss_bwd"], med["vcg_l1_fwd"] + med["vcg_l1_bwd (ga only)"]
     say(f"  forward + backward: {term} {new:.2f} us, L1 {l1:.2f} us: x {new / l1:.2f}")
+    if term == "msssim":
+        pool = med["vcg_swd_pool (1 image)"] * 2 * 4 / 3
+        say(f"  pooling, both images over all levels, about {pool:.2f} us = {pool / med['vcg_msssim_loss_fwd'] * 100:.1f} % of the forward")
     say()
 
 

@@ -1,7 +1,7 @@
 """Atomic losses with the reference's class surface (Losses.py:14-121 of the reference),
 each reduction a HIP kernel (wavefront shuffle -> block partial -> ordered final sum).
 
-Only the six atomic classes (and StructuralLoss, GradientMatchingLoss, FocalFrequencyLoss and SlicedWassersteinLoss, which the reference lacks) exist here: the reference's composite loss classes
+Only the six atomic classes (and StructuralLoss, MultiScaleStructuralLoss, GradientMatchingLoss, FocalFrequencyLoss and SlicedWassersteinLoss, which the reference lacks) exist here: the reference's composite loss classes
 (Losses.py:123-379) are dead code there and are not part of the training step.
 """
 import math
@@ -39,6 +39,22 @@ class StructuralLoss(nn.Module):
 
     def forward(self, generated, target):
         return ops.ssim_loss(generated, target)
+
+
+class MultiScaleStructuralLoss(nn.Module):
+    """1 - mean MS-SSIM(generated, target) (Wang, Simoncelli & Bovik 2003): StructuralLoss's window over `scales` in 1..5 levels
+    of a 2 x 2 mean pyramid, the contrast-structure means of the finer levels and the SSIM mean of the coarsest multiplied per
+    image and channel under the customary exponents — the structure an 11 x 11 window on the full image cannot see
+    (new: the reference has no multi-scale term).  The coarsest level must hold the window: min(H, W) >> (scales - 1) >= 11."""
+
+    def __init__(self, scales=5):
+        super().__init__()
+        if isinstance(scales, bool) or not isinstance(scales, int) or not 1 <= scales <= ops.MSSSIM_MAX_SCALES:
+            raise ValueError(f"scales must be an integer in 1..{ops.MSSSIM_MAX_SCALES}, got {scales!r}")
+        self.scales = scales
+
+    def forward(self, generated, target):
+        return ops.msssim_loss(generated, target, self.scales)
 
 
 class GradientMatchingLoss(nn.Module):

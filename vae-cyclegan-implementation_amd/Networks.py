@@ -20,7 +20,7 @@ from torch.nn.utils import spectral_norm
 
 from . import ops
 from .Losses import (IMAGE_TERMS, CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss, KLDivergenceLoss,
-                     SlicedWassersteinLoss, TranslationLoss)
+                     MultiScaleStructuralLoss, SlicedWassersteinLoss, TranslationLoss)
 from .image_pool import ImagePool, pool_seed as _pool_seed
 from .optim import FusedAdam
 
@@ -390,8 +390,9 @@ def _clip_scalars(**optimizers):
 
 def _image_terms(kwargs):
     """The optional image terms a configure_loss call switches on: ((reported name, weight, loss module), ...) for the rows of
-    Losses.IMAGE_TERMS whose lambda_<key> is > 0, in the table's order.  With a weight at its default 0 no loss object exists (the
-    term's option is then not looked at) and the step computes, launches and reports exactly what it did before the term was added."""
+    Losses.IMAGE_TERMS whose lambda_<key> is > 0, in the table's order, then the multi-scale structural term (lambda_msssim,
+    msssim_scales; reported as loss_msssim).  With a weight at its default 0 no loss object exists (the term's option is then not
+    looked at) and the step computes, launches and reports exactly what it did before the term was added."""
     active = []
     for row in IMAGE_TERMS:
         lam = float(kwargs.get(f"lambda_{row.key}", 0.0))
@@ -400,6 +401,11 @@ def _image_terms(kwargs):
         if lam > 0.0:
             option = () if row.option is None else (kwargs.get(row.option, row.default),)
             active.append((f"loss_{row.key}", lam, row.loss(*option)))
+    lam = float(kwargs.get("lambda_msssim", 0.0))
+    if not math.isfinite(lam) or lam < 0.0:
+        raise ValueError(f"lambda_msssim must be finite and >= 0, got {lam}")
+    if lam > 0.0:
+        active.append(("loss_msssim", lam, MultiScaleStructuralLoss(kwargs.get("msssim_scales", 5))))
     return tuple(active)
 
 
@@ -806,7 +812,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
             raise ValueError("KL divergence loss function has not been configured yet.")
 
     def _losses(self, batch):
-        """-> (G(x), the step's scalars in the order they are reported: G_loss, loss_trans, loss_kl, [loss_ssim], [loss_grad], [loss_freq])"""
+        """-> (G(x), the step's scalars in the order they are reported: G_loss, loss_trans, loss_kl, [loss_ssim], [loss_grad], [loss_freq], [loss_msssim])"""
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         output, mu, logvar = self(x)
         loss_trans = self.loss_trans_fn(output, y)

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # VCG_LIBVCG: load another build of the same sources (A/B runs of kernel variants, tools/); the default is the in-tree library
 LIB_PATH = os.environ.get("VCG_LIBVCG") or os.path.join(_HERE, "libvcg.so")
-SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip", "swd_loss.hip"]
+SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip", "swd_loss.hip", "msssim_loss.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vcg.h")
 
 _c = ctypes
@@ -78,6 +78,9 @@ SIGNATURES = {
     "vcg_ssim_loss_workspace": (_Z, [_I, _I, _I]),
     "vcg_ssim_loss_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _Z, _P]),
     "vcg_ssim_loss_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "vcg_msssim_loss_workspace": (_Z, [_I, _I, _I, _I]),
+    "vcg_msssim_loss_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
+    "vcg_msssim_loss_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "vcg_grad_loss_workspace": (_Z, [_I, _I, _I, _I]),
     "vcg_grad_loss_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _P]),
     "vcg_grad_loss_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
@@ -149,7 +152,8 @@ def build(force=False, verbose=False):
     if os.environ.get("VCG_LIBVCG"):
         return LIB_PATH                              # a variant build made by hand: never rebuilt here
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, "vcg_common.h"), HEADER]
+    headers = [os.path.join(CSRC, "vcg_common.h"), os.path.join(CSRC, "ssim_window.h"), HEADER]
+    deps = srcs + headers
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
             return LIB_PATH
@@ -164,7 +168,7 @@ def build(force=False, verbose=False):
     objdir = os.path.join(CSRC, "_obj")
     os.makedirs(objdir, exist_ok=True)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC"]
-    hdr_time = max(os.path.getmtime(os.path.join(CSRC, "vcg_common.h")), os.path.getmtime(HEADER))
+    hdr_time = max(os.path.getmtime(h) for h in headers)
 
     def compile_one(src):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")

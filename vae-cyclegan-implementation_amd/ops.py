@@ -1236,6 +1236,27 @@ class _SsimTerm:
         _call("vcg_ssim_loss_bwd", _ptr(ap), _ptr(bp), _ptr(g), _ptr(ga), *dims, _stream())
 
 
+class _MsssimTerm:
+    """1 - mean MS-SSIM(generated, target) (csrc/msssim_loss.hip); opt: the number of scales.  The forward keeps its workspace —
+    the pooled levels and the table d loss / d factor — for the backward, so none of it lives in the shared scratch buffer."""
+    name = "msssim_loss"
+
+    @staticmethod
+    def scratch(n, h, w, scales):
+        return 0
+
+    @staticmethod
+    def fwd(ap, bp, out, dims, scales, _):
+        keep = torch.empty(_scratch("vcg_msssim_loss_workspace", *dims, scales) // 4, dtype=torch.float32, device=ap.device)
+        _call("vcg_msssim_loss_fwd", _ptr(ap), _ptr(bp), _ptr(out), *dims, scales, _ptr(keep), keep.numel() * 4, _stream())
+        return ap, bp, keep
+
+    @staticmethod
+    def bwd(kept, g, ga, dims, scales):
+        ap, bp, keep = kept
+        _call("vcg_msssim_loss_bwd", _ptr(ap), _ptr(bp), _ptr(g), _ptr(ga), *dims, scales, _ptr(keep), keep.numel() * 4, _stream())
+
+
 class _GradTerm:
     """Multi-scale gradient-matching loss of (generated, target) (csrc/grad_loss.hip); opt: the number of scales."""
     name = "grad_match_loss"
@@ -1279,7 +1300,7 @@ class _FreqTerm:
 
 
 class _ImageLossFn(torch.autograd.Function):
-    """The loss `term` (_SsimTerm, _GradTerm, _FreqTerm) of (generated, target); the gradient reaches `generated` only."""
+    """The loss `term` (_SsimTerm, _MsssimTerm, _GradTerm, _FreqTerm) of (generated, target); the gradient reaches `generated` only."""
 
     @staticmethod
     def forward(ctx, term, a, b, opt):
@@ -1315,6 +1336,35 @@ def _image_loss(term, generated, target, opt=None):
 def ssim_loss(generated, target):
     """1 - mean SSIM over (N, 3, H, W) images, H, W >= 11: a 0-dim fp32 tensor.  `target` is an input image: no gradient."""
     return _image_loss(_SsimTerm, generated, target)
+
+
+MSSSIM_MAX_SCALES = 5
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)         # Wang, Simoncelli & Bovik 2003; the first K over their sum
+
+
+def msssim_weights(scales):
+    """The exponents of the `scales` levels of `msssim_loss`: they sum to 1."""
+    total = sum(MSSSIM_WEIGHTS[:scales])
+    return tuple(w / total for w in MSSSIM_WEIGHTS[:scales])
+
+
+def msssim_max_scales(h, w):
+    """The largest `scales` in 0..5 that `msssim_loss` accepts for H x W images: the coarsest level, min(H, W) >> (scales - 1),
+    must still hold the 11 x 11 window.  0: not even one scale.  Host arithmetic only."""
+    k = 0
+    while k < MSSSIM_MAX_SCALES and (min(int(h), int(w)) >> k) >= 11:
+        k += 1
+    return k
+
+
+def msssim_loss(generated, target, scales=5):
+    """1 - mean over images and channels of MS-SSIM (the product over `scales` in 1..5 levels of a 2 x 2 mean pyramid of the
+    mean contrast-structure, the coarsest level's mean SSIM, each clamped below at 1e-4 and raised to its weight) of (N, 3, H, W)
+    images, min(H, W) >> (scales - 1) >= 11: a 0-dim fp32 tensor.  scales = 1 is `ssim_loss`.  `target` is an input image: no
+    gradient."""
+    if isinstance(scales, bool) or int(scales) != scales or not 1 <= int(scales) <= MSSSIM_MAX_SCALES:
+        raise RuntimeError(f"msssim_loss: scales must be an integer in 1..{MSSSIM_MAX_SCALES}, got {scales!r}")
+    return _image_loss(_MsssimTerm, generated, target, int(scales))
 
 
 def grad_match_loss(generated, target, scales=4):

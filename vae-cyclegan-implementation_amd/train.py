@@ -270,6 +270,13 @@ def build_parser():
                    help="number of scales of the gradient-matching term; scale s keeps every 2^s-th pixel")
     p.add_argument("--freq_alpha", type=_nonneg("--freq_alpha", ""), default=1.0,
                    help="exponent of the focal frequency term's spectrum weight |difference|^alpha; 0: an unweighted spectral MSE")
+    p.add_argument("--lambda_msssim", type=_nonneg("--lambda_msssim", " (0: the term is not computed)"), default=0.0,
+                   help="weight of the multi-scale structural term 1 - MS-SSIM (the SSIM window over a 2x2 mean pyramid: shading, "
+                        "regional contrast and large shapes, which --lambda_ssim's one scale does not see) beside the L1 ("
+                        + ", ".join(SSIM_ARCHS) + "); 0: not computed")
+    p.add_argument("--msssim_scales", type=int, default=5, choices=(1, 2, 3, 4, 5),
+                   help="levels of the multi-scale structural term's pyramid; --image_size >> (scales - 1) must be at least 11 "
+                        "(5 scales: 176)")
     p.add_argument("--lambda_swd", type=_nonneg("--lambda_swd", " (0: the term is not computed)"), default=0.0,
                    help="weight of the sliced Wasserstein term swd(G(x), y) + swd(F(y), x): a distance between the patch "
                         "distributions of the translated batch and of the other domain's batch, which needs no pairing and no "
@@ -373,6 +380,21 @@ def main(args):
         raise ValueError(f"--grad_scales must be 1, 2, 3 or 4, got {image_kw['grad_scales']}")
     if not math.isfinite(image_kw["freq_alpha"]) or image_kw["freq_alpha"] < 0.0:
         raise ValueError(f"--freq_alpha must be finite and >= 0, got {image_kw['freq_alpha']}")
+    lambda_msssim = image_kw["lambda_msssim"] = getattr(args, "lambda_msssim", 0.0)
+    if not math.isfinite(lambda_msssim) or lambda_msssim < 0.0:
+        raise ValueError(f"--lambda_msssim must be finite and >= 0 (0: the term is not computed), got {lambda_msssim}")
+    if lambda_msssim != 0.0 and args.architecture not in SSIM_ARCHS:
+        raise ValueError(f"--lambda_msssim is supported by {', '.join(SSIM_ARCHS)} only, not by {args.architecture}: "
+                         "the flag would be ignored")
+    msssim_scales = image_kw["msssim_scales"] = getattr(args, "msssim_scales", 5)
+    if isinstance(msssim_scales, bool) or msssim_scales not in (1, 2, 3, 4, 5):
+        raise ValueError(f"--msssim_scales must be 1, 2, 3, 4 or 5, got {msssim_scales}")
+    image_size = getattr(args, "image_size", 256)
+    if lambda_msssim != 0.0 and ops.msssim_max_scales(image_size, image_size) < msssim_scales:
+        usable = ops.msssim_max_scales(image_size, image_size)
+        raise ValueError(f"--image_size {image_size} is too small for --msssim_scales {msssim_scales}: the coarsest level, "
+                         f"image_size >> (scales - 1), must hold the 11x11 window; "
+                         + (f"the largest usable --msssim_scales is {usable}" if usable else "no --msssim_scales is usable below 11"))
     lambda_swd = image_kw["lambda_swd"] = getattr(args, "lambda_swd", 0.0)
     if not math.isfinite(lambda_swd) or lambda_swd < 0.0:
         raise ValueError(f"--lambda_swd must be finite and >= 0 (0: the term is not computed), got {lambda_swd}")
