@@ -244,6 +244,26 @@ int vcg_kl_fwd(const float* mu, const float* lv, float* out, size_t n,
                void* ws, size_t ws_bytes, void* stream);
 int vcg_kl_bwd(const float* mu, const float* lv, const float* gout, float* gmu, float* glv,
                size_t n, void* stream);
+/* The same term (Losses.py:115-121) with a free-bits floor per latent channel (new: the reference has none; Kingma et al. 2016).
+   mu, lv: rows x cp fp32, the networks' NHWC latent with rows = N h w, c logical channels at pitch cp (a multiple of 4, the
+   channel the fastest index), 16-byte aligned.  Per element k = -0.5 (1 + l - mu^2 - exp(l)), l = clamp(lv, -10, 10);
+   KL_ch = mean over the rows of k.  A channel's gate is closed iff klc[ch] <= floor (a tie is closed; a NaN leaves it open).
+     out3[0] = (1 / c) sum_ch max(KL_ch, floor)      the floored objective
+     out3[1] = (1 / c) sum_ch KL_ch                  vcg_kl_fwd's mean in another summation order
+     out3[2] = the number of channels whose gate is open
+     klc[0 .. c) = KL_ch, kept by the caller for vcg_kl_fb_bwd
+   Pad lanes ch >= c are never summed, never counted in c, and get gradient 0.  floor: finite and >= 0.  ws:
+   vcg_kl_fb_workspace(rows, cp) bytes (0 and vcg_last_error for bad arguments), 16-byte aligned: one partial per (row slab,
+   channel), summed per channel in slab order in double by a final launch.  No atomics: the same input gives the same bits.
+   csrc/kl_free_bits.hip. */
+size_t vcg_kl_fb_workspace(size_t rows, int cp);
+int vcg_kl_fb_fwd(const float* mu, const float* lv, float* out3, float* klc, size_t rows, int c, int cp, float floor,
+                  void* ws, size_t ws_bytes, void* stream);
+/* With s = gout[0] / (rows c) where the channel's gate is open (recomputed from klc and floor: no mask is stored), else 0:
+   gmu = mu s;  glv = -0.5 (1 - exp(l)) s where lv lies inside [-10, 10], else 0 (vcg_kl_bwd's rule).  Both rows x cp, written
+   whole, pad lanes 0; gout is read on the device. */
+int vcg_kl_fb_bwd(const float* mu, const float* lv, const float* gout, const float* klc, float* gmu, float* glv,
+                  size_t rows, int c, int cp, float floor, void* stream);
 /* Structural loss (new: the reference trains on pixel-wise terms only): out[0] = 1 - mean SSIM(a, b) over the N images, the 3
    logical channels and the (H - 10)(W - 10) valid positions of an 11 x 11 Gaussian window (sigma 1.5, normalised to sum 1,
    C1 = 0.01^2, C2 = 0.03^2, population moments): vcg_image_metrics's definition without the clamp of either operand.  a

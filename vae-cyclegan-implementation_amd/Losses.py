@@ -180,7 +180,25 @@ class GANLossDiscriminator(nn.Module):
 
 
 class KLDivergenceLoss(nn.Module):
-    """-0.5 * mean(1 + clamp(logvar) - mu^2 - exp(clamp(logvar)))  (reference Losses.py:105-121)."""
+    """-0.5 * mean(1 + clamp(logvar) - mu^2 - exp(clamp(logvar)))  (reference Losses.py:105-121).
+
+    `free_bits` > 0 (new: the reference has no floor; Kingma et al. 2016): the value returned is mean_c max(KL_c, free_bits), KL_c
+    the mean of the same term over batch and positions of latent channel c — a channel at or below the floor is no longer
+    penalised, so none is pushed to zero information.  The call then leaves `plain` (the unfloored mean, what free_bits = 0
+    returns), `active` (the number of channels above the floor) and `channels` (their count) of its LAST call on the module, as
+    device scalars without a gradient, for the model to report.  With the default 0 it is ops.kl_loss as before."""
+
+    def __init__(self, free_bits=0.0):
+        super().__init__()
+        if isinstance(free_bits, bool) or not isinstance(free_bits, (int, float)) or not math.isfinite(free_bits) or free_bits < 0:
+            raise ValueError(f"free_bits must be a finite number >= 0, got {free_bits!r}")
+        self.free_bits = float(free_bits)
+        self.plain = self.active = None
+        self.channels = 0
 
     def forward(self, mu, logvar):
-        return ops.kl_loss(mu, logvar)
+        if self.free_bits == 0.0:
+            return ops.kl_loss(mu, logvar)
+        loss, self.plain, self.active = ops.kl_free_bits(mu, logvar, self.free_bits)
+        self.channels = mu.shape[1]
+        return loss

@@ -13,6 +13,7 @@ NHWC (pitch 4 for 3-channel images); NCHW-contiguous inputs are converted on ent
 """
 import contextlib
 import math
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -22,7 +23,7 @@ from . import ops
 from .Losses import (IMAGE_TERMS, CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss, KLDivergenceLoss,
                      MultiScaleStructuralLoss, SlicedWassersteinLoss, TranslationLoss)
 from .image_pool import ImagePool, pool_seed as _pool_seed
-from .optim import FusedAdam
+from .optim import FusedAdam, kl_weight_at
 
 _ACTS = {"ReLU": ops.ACT_RELU, "LeakyReLU": ops.ACT_LEAKY, "Identity": ops.ACT_NONE, "Tanh": ops.ACT_TANH, "Sigmoid": ops.ACT_SIGMOID}
 
@@ -479,6 +480,119 @@ class _SwdMixin:
         self.swd_term[1].load_state_dict(state)
 
 
+KL_MODELS = "vae, vaegan, cyclevae, cyclevaegan and doublevae"      # the models with a latent distribution and a KL term
+
+
+class KlControl(NamedTuple):
+    """configure_loss's keywords that shape the KL term of a variational model beyond its weight lambda_kl.  kl_free_bits: the
+    free-bits floor per latent channel (Losses.KLDivergenceLoss); kl_anneal_steps, kl_cycles, kl_ramp: the schedule of the weight
+    over the generator optimizer's steps (optim.kl_weight_at).  The defaults switch both off: the step then computes, launches
+    and reports exactly what it did before the options existed."""
+    free_bits: float = 0.0
+    anneal_steps: int = 0
+    cycles: int = 1
+    ramp: float = 1.0
+
+
+_KL_OFF = KlControl()
+
+
+def _kl_control(kwargs):
+    """The validated KlControl of a configure_loss call."""
+    def number(name, default):
+        v = kwargs.get(name, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        return v
+
+    def integer(name, default, least):
+        v = number(name, default)
+        if int(v) != v or int(v) < least:
+            raise ValueError(f"{name} must be an integer >= {least}, got {v!r}")
+        return int(v)
+
+    free_bits = float(number("kl_free_bits", 0.0))
+    if free_bits < 0.0:
+        raise ValueError(f"kl_free_bits must be >= 0 (0: no floor), got {free_bits}")
+    steps = integer("kl_anneal_steps", 0, 0)
+    cycles = integer("kl_cycles", 1, 1)
+    ramp = float(number("kl_ramp", 1.0))
+    if not 0.0 < ramp <= 1.0:
+        raise ValueError(f"kl_ramp must lie in (0, 1], got {ramp}")
+    return KlControl(free_bits, steps, cycles, ramp)
+
+
+def _refuse_kl_control(model, kwargs):
+    """configure_loss of the models without a latent distribution takes the keywords so that one call fits every architecture:
+    the defaults are ignored."""
+    control = _kl_control(kwargs)
+    if control != _KL_OFF:
+        given = ", ".join(f"kl_{k}={v}" for k, v, d in zip(control._fields, control, _KL_OFF) if v != d)
+        raise ValueError(f"{given}: {type(model).__name__} has no KL term to control ({KL_MODELS} have)")
+
+
+def _configure_kl(model, kwargs):
+    """-> the KL loss module of a variational model's configure_loss; leaves `kl_control` and `lambda_kl` on the model."""
+    model.kl_control = _kl_control(kwargs)
+    model.lambda_kl = kwargs.get("lambda_kl", 1e-5)
+    return KLDivergenceLoss(model.kl_control.free_bits)
+
+
+def _kl_weight(model, training):
+    """The weight of the KL term in this step's G_loss.  A training step of a model that anneals reads the schedule at the number
+    of steps its generator optimizer has completed (checkpoints restore that counter, so a resumed run continues the schedule) and
+    leaves the value in `kl_weight_used` for the report; validation always weighs with the full lambda_kl, so its losses mean
+    the same in every epoch.  A Python float either way, as lambda_kl is."""
+    control = getattr(model, "kl_control", _KL_OFF)
+    if not training or control.anneal_steps == 0:
+        return model.lambda_kl
+    opt = getattr(model, "optimizer_G", None)
+    if opt is None:
+        opt = model.optimizer
+    model.kl_weight_used = kl_weight_at(model.lambda_kl, opt.step_count, control.anneal_steps, control.cycles, control.ramp)
+    return model.kl_weight_used
+
+
+def _kl_terms(fn, pairs):
+    """The KL loss module `fn` on the (mu, logvar) pairs of a step -> (the step's KL scalars, the term that enters G_loss, the
+    plain KL of every pair).  Without a floor: {"loss_kl": the sum over the pairs}, which is also the objective.  With one: loss_kl
+    stays the plain sum — the number that is comparable across runs —, loss_kl_fb is the sum of the floored terms and the
+    objective, kl_active the fraction of channels above the floor, averaged over the pairs."""
+    def total(values):
+        return values[0] if len(values) == 1 else ops.weighted_sum(values, [1.0] * len(values))
+
+    if fn.free_bits == 0.0:
+        values = [fn(mu, logvar) for mu, logvar in pairs]
+        t = {"loss_kl": total(values)}
+        return t, t["loss_kl"], values
+    floored, plains, actives, fractions = [], [], [], []
+    for mu, logvar in pairs:
+        floored.append(fn(mu, logvar))
+        plains.append(fn.plain)
+        actives.append(fn.active)
+        fractions.append(1.0 / (fn.channels * len(pairs)))
+    t = {"loss_kl": total(plains), "loss_kl_fb": total(floored), "kl_active": ops.weighted_sum(actives, fractions)}
+    return t, t["loss_kl_fb"], plains
+
+
+def _kl_keys(model, spec, training):
+    """`spec` (_report) with the keys the KL options add, directly after loss_kl: loss_kl_fb and kl_active with a floor, then
+    kl_weight (a host value: `_kl_host`) in the training steps of a model that anneals.  Unchanged with the options off."""
+    control = getattr(model, "kl_control", _KL_OFF)
+    extra = (_same("loss_kl_fb", "kl_active") if control.free_bits > 0.0 else ()) \
+        + ((("kl_weight", None),) if training and control.anneal_steps else ())
+    if not extra:
+        return spec
+    at = [name for name, _ in spec].index("loss_kl") + 1
+    return spec[:at] + extra + spec[at:]
+
+
+def _kl_host(model, training):
+    """_report's keyword for the kl_weight entry of `_kl_keys`: the weight the step used; it never was on the device."""
+    control = getattr(model, "kl_control", _KL_OFF)
+    return {"kl_weight": float(model.kl_weight_used)} if training and control.anneal_steps else {}
+
+
 def _backward_and_step(loss, optimizer, reducer):
     """zero_grad -> backward -> [data-parallel gradient exchange, its buckets launched from inside the backward] -> step."""
     optimizer.zero_grad()
@@ -694,6 +808,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
 
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
+        _refuse_kl_control(self, kwargs)
         self.loss_fn = TranslationLoss()
         self.image_terms = _image_terms(kwargs)
 
@@ -799,8 +914,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
-        self.loss_kl_fn = KLDivergenceLoss()
-        self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
+        self.loss_kl_fn = _configure_kl(self, kwargs)
         self.image_terms = _image_terms(kwargs)
 
     def _check_configured(self):
@@ -811,29 +925,33 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
         if self.loss_kl_fn is None:
             raise ValueError("KL divergence loss function has not been configured yet.")
 
-    def _losses(self, batch):
-        """-> (G(x), the step's scalars in the order they are reported: G_loss, loss_trans, loss_kl, [loss_ssim], [loss_grad], [loss_freq], [loss_msssim])"""
+    def _losses(self, batch, training=False):
+        """-> (G(x), the step's scalars in the order they are reported: G_loss, loss_trans, loss_kl, [loss_kl_fb, kl_active],
+        [loss_ssim], [loss_grad], [loss_freq], [loss_msssim])"""
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         output, mu, logvar = self(x)
         loss_trans = self.loss_trans_fn(output, y)
-        loss_kl = self.loss_kl_fn(mu, logvar)
+        kl, kl_objective, _ = _kl_terms(self.loss_kl_fn, [(mu, logvar)])
         extra, weights = _eval_image_terms(self.image_terms, [(output, y)])
-        named = {"G_loss": None, "loss_trans": loss_trans, "loss_kl": loss_kl, **extra}
-        named["G_loss"] = ops.weighted_sum([loss_trans, loss_kl, *extra.values()], [1.0, self.lambda_kl, *weights])
+        named = {"G_loss": None, "loss_trans": loss_trans, **kl, **extra}
+        named["G_loss"] = ops.weighted_sum([loss_trans, kl_objective, *extra.values()], [1.0, _kl_weight(self, training), *weights])
         return output, named
+
+    def _spec(self, named, training):
+        return _kl_keys(self, _same(*(k for k in named if k not in ("loss_kl_fb", "kl_active"))), training)
 
     def training_step(self, batch):
         _refuse_training_in_ema_scope(self)
         self._check_configured()
-        _, named = self._losses(batch)
+        _, named = self._losses(batch, True)
         _backward_and_step(named["G_loss"], self.optimizer, self.grad_reducer)
-        return _report(self, named, _same(*named), True)
+        return _report(self, named, self._spec(named, True), True, **_kl_host(self, True))
 
     def validation_step(self, batch):
         self._check_configured()
         with torch.no_grad():
             output, named = self._losses(batch)
-            return _report(self, named, _same(*named) + _GX, False, Gx=output)
+            return _report(self, named, self._spec(named, False) + _GX, False, Gx=output)
 
 
 # --------------------------------------------------------------------------- the two translation directions
@@ -999,8 +1117,9 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
         if self.paired:
             self.loss_identity = IdentityLoss()
         if self._variational:
-            self.loss_kl = KLDivergenceLoss()
-            self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
+            self.loss_kl = _configure_kl(self, kwargs)
+        else:
+            _refuse_kl_control(self, kwargs)
         self.lambda_gan = kwargs.get("lambda_gan", 1.0)
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
@@ -1027,7 +1146,7 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
             return vae(image)[0]
         self._skip_vae(image, vae)
 
-    def _generator_losses(self, x, y, two_streams=False):
+    def _generator_losses(self, x, y, two_streams=False, training=False):
         """Forward of both generators and everything G_loss needs (reference :1997-2018, CycleAEGAN :1733-1753).  `two_streams`
         (training_step asks for it when the weight gradients overlap too): the unpaired forward with x -> G -> F -> DY on the
         caller's stream and y -> F -> G -> DX on a second one (_two_directions); the eps draws are reserved in the reference's
@@ -1054,9 +1173,10 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
         t["loss_gan_g"] = ops.weighted_sum([t[k] for k in self._GAN_G_TERMS], [1.0] * len(self._GAN_G_TERMS))
         terms, weights = [t["loss_cycle"], t["loss_gan_g"]], [self.lambda_cycle, self.lambda_gan]
         if self._variational:
-            t["loss_kl"] = ops.weighted_sum([self.loss_kl(stats[2 * i], stats[2 * i + 1]) for i in range(4)], [1.0] * 4)
-            terms.append(t["loss_kl"])
-            weights.append(self.lambda_kl)
+            kl, kl_objective, _ = _kl_terms(self.loss_kl, [(stats[2 * i], stats[2 * i + 1]) for i in range(4)])
+            t.update(kl)
+            terms.append(kl_objective)
+            weights.append(_kl_weight(self, training))
         if self.paired:
             if not self._variational:            # CycleAEGAN's identity passes follow the discriminators (reference :1749-1751)
                 Fx, Gy = self.F(x), self.G(y)
@@ -1088,7 +1208,8 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
         if self.paired:
             keys += ("loss_identity",)
         keys += tuple(name for name, _, _ in self.image_terms)
-        return (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + self._swd_spec() + (() if training else _GX_FY)
+        return _kl_keys(self, (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + self._swd_spec() + (() if training else _GX_FY),
+                        training)
 
     def _pooled_d_terms(self, t, Gx, Fy):
         """The discriminators' fake terms with image history pools (_PoolMixin), after the forward (both direction streams are
@@ -1112,11 +1233,11 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
         self._check_configured()
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         self.optimizer_G.zero_grad()
-        t, Gx, Fy = self._generator_losses(x, y, two_streams=ops.two_directions())
+        t, Gx, Fy = self._generator_losses(x, y, two_streams=ops.two_directions(), training=True)
         if self.image_pools:
             self._pooled_d_terms(t, Gx, Fy)
         self._alternating_step(t["G_loss"], t["D_loss"])
-        return _report(self, t, self._report_spec(True), True)
+        return _report(self, t, self._report_spec(True), True, **_kl_host(self, True))
 
     def validation_step(self, batch):
         self._check_configured(need_opt=False)
@@ -1196,16 +1317,17 @@ class _CycleNoGAN(_SwdMixin, _OptimizerStatesMixin, nn.Module):
         if need_opt and self.optimizer is None:
             raise ValueError("Optimizer has not been configured yet.")
 
-    def _losses(self, batch):
+    def _losses(self, batch, training=False):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         fw = self._fwd(x, y, ops.two_directions())     # (a bare model(x, y) stays on one stream: its caller may use a plain backward)
         Gx, FGx, Fy, GFy = fw[:4]
         t = {"loss_cycle": self.loss_cycle(x, y, FGx, GFy)}
         terms, weights = [t["loss_cycle"]], [self.lambda_cycle]
         if self._variational:
-            t["loss_kl"] = ops.weighted_sum([self.loss_kl(fw[4 + 2 * i], fw[5 + 2 * i]) for i in range(4)], [1.0] * 4)
-            terms.append(t["loss_kl"])
-            weights.append(self.lambda_kl)
+            kl, kl_objective, _ = _kl_terms(self.loss_kl, [(fw[4 + 2 * i], fw[5 + 2 * i]) for i in range(4)])
+            t.update(kl)
+            terms.append(kl_objective)
+            weights.append(_kl_weight(self, training))
         if self.paired:
             t["loss_trans"] = ops.weighted_sum([self.loss_trans(Gx, y), self.loss_trans(Fy, x)], [1.0, 1.0])
             terms.append(t["loss_trans"])
@@ -1217,15 +1339,15 @@ class _CycleNoGAN(_SwdMixin, _OptimizerStatesMixin, nn.Module):
     def _report_spec(self, training):
         """the reference's key order (:1421-1433, :1547-1561): total_loss, loss_cycle, [loss_kl], G_loss, [Gx, Fy], [loss_trans],
         then [loss_swd]"""
-        return ((("total_loss", "G_loss"),) + _same("loss_cycle", *(("loss_kl",) if self._variational else ()), "G_loss")
-                + (() if training else _GX_FY) + (_same("loss_trans") if self.paired else ()) + self._swd_spec())
+        return _kl_keys(self, (("total_loss", "G_loss"),) + _same("loss_cycle", *(("loss_kl",) if self._variational else ()), "G_loss")
+                        + (() if training else _GX_FY) + (_same("loss_trans") if self.paired else ()) + self._swd_spec(), training)
 
     def training_step(self, batch):
         _refuse_training_in_ema_scope(self)
         self._check_configured()
-        t, _, _ = self._losses(batch)
+        t, _, _ = self._losses(batch, True)
         _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
-        return _report(self, t, self._report_spec(True), True)
+        return _report(self, t, self._report_spec(True), True, **_kl_host(self, True))
 
     def validation_step(self, batch):
         self._check_configured(need_opt=False)
@@ -1250,6 +1372,7 @@ class CycleAE(_CycleNoGAN):
             self.loss_trans = TranslationLoss()
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
         self._configure_swd(kwargs)
+        _refuse_kl_control(self, kwargs)
 
 
 class CycleVAE(_CycleNoGAN):
@@ -1267,8 +1390,7 @@ class CycleVAE(_CycleNoGAN):
         self.loss_cycle = CycleConsistencyLoss()
         if self.paired:
             self.loss_trans = TranslationLoss()
-        self.loss_kl = KLDivergenceLoss()
-        self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
+        self.loss_kl = _configure_kl(self, kwargs)
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
         self._configure_swd(kwargs)
 
@@ -1285,16 +1407,17 @@ class _DoubleStep(_OptimizerStatesMixin, nn.Module):
     def training_step(self, batch):
         _refuse_training_in_ema_scope(self)
         self._check_configured()
-        t, _, _ = self._losses(batch)
+        t, _, _ = self._losses(batch, True)
         _backward_and_step(t["G_loss"], self.optimizer, self.grad_reducer)
-        return _report(self, t, self._TRAIN, True)
+        return _report(self, t, _kl_keys(self, self._TRAIN, True), True, **_kl_host(self, True))
 
     def validation_step(self, batch):
         """Gx / Fy are the translations: the encoder runs four times, and a VAE draws eps for each."""
         self._check_configured(need_opt=False)
         with torch.no_grad():
             t, x, y = self._losses(batch)
-            return _report(self, t, self._VALIDATION, False, Gx=self.translate_A_to_B(x), Fy=self.translate_B_to_A(y))
+            return _report(self, t, _kl_keys(self, self._VALIDATION, False), False, Gx=self.translate_A_to_B(x),
+                           Fy=self.translate_B_to_A(y))
 
 
 class DoubleAutoencoder(_DoubleStep):
@@ -1341,6 +1464,7 @@ class DoubleAutoencoder(_DoubleStep):
 
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
+        _refuse_kl_control(self, kwargs)
         self.loss_fn = TranslationLoss()
 
     def _check_configured(self, need_opt=True):
@@ -1349,7 +1473,7 @@ class DoubleAutoencoder(_DoubleStep):
         if need_opt and self.optimizer is None:
             raise ValueError("Optimizer has not been configured yet.")
 
-    def _losses(self, batch):
+    def _losses(self, batch, training=False):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         Gx, Gy = self._fwd(x, y, ops.two_directions())
         t = {"loss_recon_A": self.loss_fn(Gx, x), "loss_recon_B": self.loss_fn(Gy, y)}
@@ -1445,8 +1569,7 @@ class DoubleVariationalAutoencoder(_DoubleStep):
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
-        self.loss_kl_fn = KLDivergenceLoss()
-        self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
+        self.loss_kl_fn = _configure_kl(self, kwargs)
 
     def _check_configured(self, need_opt=True):
         if self.loss_trans_fn is None or self.loss_kl_fn is None:
@@ -1454,13 +1577,13 @@ class DoubleVariationalAutoencoder(_DoubleStep):
         if need_opt and self.optimizer is None:
             raise ValueError("Optimizer has not been configured yet.")
 
-    def _losses(self, batch):
+    def _losses(self, batch, training=False):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         Gx, Gy, mu_x, logvar_x, mu_y, logvar_y = self._fwd(x, y, ops.two_directions())
-        t = {"loss_recon_A": self.loss_trans_fn(Gx, x), "loss_recon_B": self.loss_trans_fn(Gy, y),
-             "loss_kl_A": self.loss_kl_fn(mu_x, logvar_x), "loss_kl_B": self.loss_kl_fn(mu_y, logvar_y)}
-        t["loss_kl"] = ops.weighted_sum([t["loss_kl_A"], t["loss_kl_B"]], [1.0, 1.0])
-        t["G_loss"] = ops.weighted_sum([t["loss_recon_A"], t["loss_recon_B"], t["loss_kl"]], [1.0, 1.0, self.lambda_kl])
+        t = {"loss_recon_A": self.loss_trans_fn(Gx, x), "loss_recon_B": self.loss_trans_fn(Gy, y)}
+        kl, kl_objective, (t["loss_kl_A"], t["loss_kl_B"]) = _kl_terms(self.loss_kl_fn, [(mu_x, logvar_x), (mu_y, logvar_y)])
+        t.update(kl)                             # loss_kl_A / loss_kl_B stay each side's plain KL under a floor, as loss_kl does
+        t["G_loss"] = ops.weighted_sum([t["loss_recon_A"], t["loss_recon_B"], kl_objective], [1.0, 1.0, _kl_weight(self, training)])
         return t, x, y
 
 
@@ -1500,16 +1623,16 @@ class _SingleGAN(_GanMixin, nn.Module):
         _refuse_training_in_ema_scope(self)
         self._check_configured()
         self.optimizer_G.zero_grad()
-        t, Gx = self._losses(batch)
+        t, Gx = self._losses(batch, True)
         if self.image_pools:
             self._pooled_d_terms(t, Gx)
         self._alternating_step(t["G_loss"], t.get("D_loss_backward", t["D_loss"]))
-        return _report(self, t, self._TRAIN, True)
+        return _report(self, t, _kl_keys(self, self._TRAIN, True), True, **_kl_host(self, True))
 
     def validation_step(self, batch):
         with torch.no_grad():
             t, Gx = self._losses(batch)
-            return _report(self, t, self._VALIDATION, False, Gx=Gx)
+            return _report(self, t, _kl_keys(self, self._VALIDATION, False), False, Gx=Gx)
 
 
 class AEGAN(_SingleGAN):
@@ -1547,6 +1670,7 @@ class AEGAN(_SingleGAN):
 
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
+        _refuse_kl_control(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
         self.loss_gan_gen_fn = GANLossGenerator()
         self.loss_gan_disc_fn = GANLossDiscriminator()
@@ -1566,7 +1690,7 @@ class AEGAN(_SingleGAN):
         if self.loss_identity_fn is None:
             raise ValueError("Identity loss function has not been configured yet.")
 
-    def _losses(self, batch):
+    def _losses(self, batch, training=False):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         Gx, Gy, DGx, Dy = self(x, y)
         t = {"loss_trans": self.loss_trans_fn(Gx, y), "loss_identity": self.loss_identity_fn(Gy, y)}
@@ -1611,10 +1735,9 @@ class VAEGAN(_SingleGAN):
         self.gan_loss_gen = GANLossGenerator()
         self.gan_loss_disc = GANLossDiscriminator()
         self.identity_loss = TranslationLoss()
-        self.kl_loss = KLDivergenceLoss()
+        self.kl_loss = _configure_kl(self, kwargs)
         self.lambda_gan = kwargs.get("lambda_gan", 1.0)
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
-        self.lambda_kl = kwargs.get("lambda_kl", 1e-5)
         self.lambda_recon = kwargs.get("lambda_recon", 1.0)
 
     def enable_debug_mode(self, enabled=True):
@@ -1624,14 +1747,15 @@ class VAEGAN(_SingleGAN):
         if self.optimizer_G is None or self.optimizer_D is None:
             raise ValueError("Optimizers have not been configured yet.")
 
-    def _losses(self, batch):
+    def _losses(self, batch, training=False):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
         Gx, mu, logvar, Gy, _, _, DGx, Dy = self(x, y)
-        t = {"loss_trans": self.translation_loss(Gx, y), "loss_identity": self.identity_loss(Gy, y),
-             "loss_kl": self.kl_loss(mu, logvar)}
+        t = {"loss_trans": self.translation_loss(Gx, y), "loss_identity": self.identity_loss(Gy, y)}
+        kl, kl_objective, _ = _kl_terms(self.kl_loss, [(mu, logvar)])
+        t.update(kl)
         self._gan_terms(t, DGx, Dy)
-        t["G_loss"] = ops.weighted_sum([t["loss_trans"], t["gan_g"], t["loss_identity"], t["loss_kl"]],
-                                       [self.lambda_recon, self.lambda_gan, self.lambda_identity, self.lambda_kl])
+        t["G_loss"] = ops.weighted_sum([t["loss_trans"], t["gan_g"], t["loss_identity"], kl_objective],
+                                       [self.lambda_recon, self.lambda_gan, self.lambda_identity, _kl_weight(self, training)])
         # the reference detaches the discriminator OUTPUT of the fake branch (`gan_loss_disc(Dy, DGx.detach())`, :1277),
         # not its input: the fake term is a constant in D_loss and only (1 - D(y))^2 reaches D's parameters.  Kept as
         # written — D_loss reports both terms, the backward pass sees the real one.

@@ -1458,6 +1458,74 @@ def kl_loss(mu, logvar):
     return _KLFn.apply(mu, logvar)
 
 
+def _kl_fb_phys(t):
+    """mu or logvar of `kl_free_bits` -> its physical (N, h, w, pitch(C)) buffer: an (N, C, h, w) latent of the networks in place
+    (pad lanes included: the kernels never sum them), anything else — a 2-D (N, C) tensor as (N, C, 1, 1), another layout, a
+    tensor whose pad lanes are not the package's — through the dense copy `as_phys` makes."""
+    if t.dim() == 2:
+        t = t.reshape(t.shape[0], t.shape[1], 1, 1)
+    elif t.dim() != 4:
+        raise RuntimeError(f"kl_free_bits: expected an (N, C, h, w) or (N, C) latent, got shape {tuple(t.shape)}")
+    if t.numel() == 0:
+        raise RuntimeError(f"kl_free_bits: empty latent of shape {tuple(t.shape)}")
+    return as_phys(t)
+
+
+class _KLFreeBitsFn(torch.autograd.Function):
+    """KLDivergenceLoss.forward (Losses.py:115-121) with a free-bits floor per channel (csrc/kl_free_bits.hip) ->
+    (floored mean, plain mean, open gates, the (C,) channel KLs); the gradient reaches mu and logvar through the floored mean only."""
+
+    @staticmethod
+    def forward(ctx, mu, lv, floor):
+        if mu.shape != lv.shape:
+            raise RuntimeError(f"shape mismatch {tuple(mu.shape)} vs {tuple(lv.shape)}")
+        mup, lvp = _kl_fb_phys(mu), _kl_fb_phys(lv)
+        n, h, w, cp = mup.shape
+        rows, c = n * h * w, mu.shape[1]
+        out = torch.empty(3, dtype=torch.float32, device=mu.device)
+        klc = torch.empty(c, dtype=torch.float32, device=mu.device)
+        ws = workspace(_scratch("vcg_kl_fb_workspace", rows, cp), mu.device)
+        _call("vcg_kl_fb_fwd", _ptr(mup), _ptr(lvp), _ptr(out), _ptr(klc), rows, c, cp, floor, _ptr(ws), ws.numel() * 4, _stream())
+        ctx.save_for_backward(mup, lvp, klc)
+        ctx.call = (rows, c, cp, floor, tuple(mu.shape))
+        loss, plain, active = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(plain, active, klc)
+        return loss, plain, active, klc
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gplain, _gactive, _gklc):
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None
+        mup, lvp, klc = ctx.saved_tensors
+        rows, c, cp, floor, shape = ctx.call
+        g = g.contiguous()
+        gmu, glv = torch.empty_like(mup), torch.empty_like(lvp)
+        _call("vcg_kl_fb_bwd", _ptr(mup), _ptr(lvp), _ptr(g), _ptr(klc), _ptr(gmu), _ptr(glv), rows, c, cp, floor, _stream())
+
+        def view(t, wanted):
+            if not wanted:
+                return None
+            t = logical_of(t, c)
+            return t if len(shape) == 4 else t.reshape(shape)
+        return view(gmu, ctx.needs_input_grad[0]), view(glv, ctx.needs_input_grad[1]), None
+
+
+def kl_free_bits(mu, logvar, floor, channel_kl=False):
+    """The KL term with a free-bits floor (Kingma et al. 2016) -> (loss, plain, active), 0-dim fp32 tensors.  With KL_c the mean
+    over batch and positions of -0.5 (1 + l - mu^2 - exp(l)), l = clamp(logvar, -10, 10), of channel c (dimension 1):
+    loss = mean_c max(KL_c, floor), differentiable once in mu and logvar — a channel at or below the floor passes no gradient;
+    plain = mean_c KL_c, `kl_loss`'s value; active = the number of channels above the floor.  plain and active carry no
+    gradient.  channel_kl=True appends the (C,) tensor of the KL_c."""
+    floor = float(floor)
+    if not math.isfinite(floor) or floor < 0.0:
+        raise RuntimeError(f"kl_free_bits: the floor must be finite and >= 0, got {floor!r}")
+    _require_gpu(mu, "kl_free_bits")
+    _require_gpu(logvar, "kl_free_bits")
+    out = _KLFreeBitsFn.apply(mu, logvar, floor)
+    return out if channel_kl else out[:3]
+
+
 class _LinCombFn(torch.autograd.Function):
     """sum_i w_i * s_i over scalar device tensors (the composite-loss lines Networks.py:941, 2012-2018)."""
 

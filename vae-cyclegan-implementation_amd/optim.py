@@ -37,6 +37,19 @@ def ema_decay_at(ema_decay, updates):
     return min(float(ema_decay), (1.0 + k) / (10.0 + k))
 
 
+def kl_weight_at(lambda_kl, t, anneal_steps, cycles=1, ramp=1.0):
+    """The KL weight of the training step that follows `t` completed generator-optimizer steps.  anneal_steps == 0: lambda_kl,
+    always.  Otherwise `cycles` cycles of anneal_steps steps each: within a cycle the weight climbs linearly from 0 over the first
+    ramp * anneal_steps steps and stays at lambda_kl for the rest,
+        lambda_kl * min(1, ((t mod anneal_steps) / anneal_steps) / ramp)    for t < cycles * anneal_steps,
+    and after the last cycle it is lambda_kl.  cycles = 1, ramp = 1: the monotone linear warm-up (Bowman et al. 2016);
+    cycles = 4, ramp = 0.5: the cyclical schedule of Fu et al. 2019.  Host arithmetic only."""
+    lambda_kl, t, anneal_steps, cycles = float(lambda_kl), int(t), int(anneal_steps), int(cycles)
+    if anneal_steps == 0 or t >= cycles * anneal_steps:
+        return lambda_kl
+    return lambda_kl * min(1.0, ((max(t, 0) % anneal_steps) / anneal_steps) / float(ramp))
+
+
 class FusedAdam:
     """`max_grad_norm=None`: plain Adam, the launches it always made.  A positive finite float: every step() first measures
     `grad_scale * ||flat_grad||_2` (the gradient Adam sees: the global-batch gradient under data parallelism; the alignment

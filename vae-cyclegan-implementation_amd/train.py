@@ -45,6 +45,8 @@ REFERENCE_ARCHS = ["autoencoder", "doubleae", "doublevae", "vae", "aegan", "vaeg
 BUILT = tuple(REFERENCE_ARCHS)
 SSIM_ARCHS = ("autoencoder", "vae", "cycleaegan", "cyclevaegan")     # the models whose configure_loss takes Losses.IMAGE_TERMS (named for the first)
 SWD_ARCHS = ("cycleae", "cyclevae", "cycleaegan", "cyclevaegan")       # the models whose configure_loss builds the sliced Wasserstein term
+KL_ARCHS = ("vae", "vaegan", "cyclevae", "cyclevaegan", "doublevae")    # the models with a KL term (Networks.KL_MODELS)
+KL_DEFAULTS = {"kl_free_bits": 0.0, "kl_anneal_steps": 0, "kl_cycles": 1, "kl_ramp": 1.0}
 IMAGE_TERM_HELP = {                  # --lambda_<key>, per row of Losses.IMAGE_TERMS
     "ssim": "weight of the structural term 1 - SSIM",
     "grad": "weight of the multi-scale gradient-matching term (an L1 on the finite differences of generated - target)",
@@ -216,6 +218,51 @@ def _nonneg(flag, meaning):
     return parse
 
 
+def _at_least(flag, least, meaning):
+    """argparse type of --kl_anneal_steps and --kl_cycles: an integer >= `least`."""
+    def parse(text):
+        try:
+            value = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+        if value < least:
+            raise argparse.ArgumentTypeError(f"{flag} must be an integer >= {least}{meaning}, got {text}")
+        return value
+    return parse
+
+
+def kl_ramp_value(text):
+    """argparse type of --kl_ramp: a finite share of a cycle in (0, 1]."""
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not math.isfinite(value) or not 0.0 < value <= 1.0:
+        raise argparse.ArgumentTypeError(f"--kl_ramp must be finite and lie in (0, 1], got {text}")
+    return value
+
+
+def kl_control_of(args):
+    """configure_loss's KL keywords from `args` (also one built without the parser), checked as the parser checks them and
+    refused for an architecture without a KL term."""
+    kw = {name: getattr(args, name, default) for name, default in KL_DEFAULTS.items()}
+    for name in kw:
+        if isinstance(kw[name], bool) or not isinstance(kw[name], (int, float)) or not math.isfinite(kw[name]):
+            raise ValueError(f"--{name} must be a finite number, got {kw[name]!r}")
+    if kw["kl_free_bits"] < 0.0:
+        raise ValueError(f"--kl_free_bits must be finite and >= 0 (0: no floor), got {kw['kl_free_bits']}")
+    for name, least in (("kl_anneal_steps", 0), ("kl_cycles", 1)):
+        if int(kw[name]) != kw[name] or kw[name] < least:
+            raise ValueError(f"--{name} must be an integer >= {least}, got {kw[name]}")
+    if not 0.0 < kw["kl_ramp"] <= 1.0:
+        raise ValueError(f"--kl_ramp must be finite and lie in (0, 1], got {kw['kl_ramp']}")
+    given = [name for name, default in KL_DEFAULTS.items() if kw[name] != default]
+    if given and args.architecture not in KL_ARCHS:
+        raise ValueError(f"--{given[0]} is supported by {', '.join(KL_ARCHS)} only, not by {args.architecture}: it has no KL term, "
+                         "the flag would be ignored")
+    return kw
+
+
 def ema_decay_value(text):
     """argparse type of --ema_decay: a finite decay in [0, 1) (0: off)."""
     try:
@@ -283,6 +330,19 @@ def build_parser():
                         "discriminator (" + ", ".join(SWD_ARCHS) + "); 0: not computed")
     p.add_argument("--swd_levels", type=int, default=3, choices=(1, 2, 3),
                    help="levels of the sliced Wasserstein term's 2x2 box pyramid (a level needs sides of at least 16)")
+    p.add_argument("--kl_free_bits", type=_nonneg("--kl_free_bits", " (0: no floor)"), default=0.0,
+                   help="free-bits floor of the KL term, in nats per latent channel (" + ", ".join(KL_ARCHS) + "): a channel whose "
+                        "mean KL is at or below it is no longer penalised, so none collapses to zero information; loss_kl stays "
+                        "the plain KL, loss_kl_fb and kl_active report the floored term and the share of channels above the "
+                        "floor; 0: no floor")
+    p.add_argument("--kl_anneal_steps", type=_at_least("--kl_anneal_steps", 0, " (0: a constant weight)"), default=0,
+                   help="anneal the KL weight: climb from 0 to --lambda_kl over this many generator steps per cycle (kl_weight "
+                        "reports it; validation always uses the full weight; --resume continues the schedule); 0: constant")
+    p.add_argument("--kl_cycles", type=_at_least("--kl_cycles", 1, ""), default=1,
+                   help="number of annealing cycles of --kl_anneal_steps steps each (1: one warm-up; 4 with --kl_ramp 0.5: the "
+                        "cyclical schedule), after which the weight stays at --lambda_kl")
+    p.add_argument("--kl_ramp", type=kl_ramp_value, default=1.0,
+                   help="share of each annealing cycle spent climbing; the weight is --lambda_kl for the rest of the cycle")
     p.add_argument("--clip_grad_norm", type=clip_bound, default=0.0,
                    help="clip each optimizer's gradient to this global 2-norm inside the fused Adam step (every architecture); "
                         "a step whose gradient holds a NaN / Inf is skipped; 0: off")
@@ -404,6 +464,7 @@ def main(args):
     image_kw["swd_levels"] = getattr(args, "swd_levels", 3)
     if image_kw["swd_levels"] not in (1, 2, 3):
         raise ValueError(f"--swd_levels must be 1, 2 or 3, got {image_kw['swd_levels']}")
+    kl_kw = kl_control_of(args)
     clip = getattr(args, "clip_grad_norm", 0.0)
     if not math.isfinite(clip) or clip < 0.0:
         raise ValueError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {clip}")
@@ -472,7 +533,7 @@ def main(args):
         print(f"Averaged generator weights (decay {ema_decay}): the test loss, and with it best_model.pth, is the averaged weights'")
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
                          lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
-                         swd_seed=ops.rank_seed(args.seed, rank) % 2 ** 32, **image_kw)      # plans per rank, as the eps streams
+                         swd_seed=ops.rank_seed(args.seed, rank) % 2 ** 32, **image_kw, **kl_kw)      # plans per rank, as the eps streams
     if world > 1:
         parallel.attach(model)
     same_xy = args.architecture in ("autoencoder", "vae")
