@@ -43,13 +43,24 @@ from test_gpu_parity import DP_LR, LAMBDAS, LR, STEP_BIAS_STD, _check_metrics, l
 
 pytestmark = pytest.mark.gpu
 
-SIZE = {"autoencoder": 64, "vae": 64, "cyclevaegan": 256}      # the smallest the goldens use; the discriminators' 16 x 16 full-map
-#                                                                layer admits nothing below 256
-SYNTH_KEY = {"autoencoder": "ae64", "vae": "vae64", "cyclevaegan": "dp"}      # the weight streams of the golden steps
+# The tables below are keyed by case: an architecture of train.py, "-paired" appended for a cycle model with paired=True (a bare
+# cycle name is the unpaired model).  tests/test_gpu_dp_architectures.py runs the cases this file's own tests do not.
+GAN_ARCHS = ("aegan", "vaegan", "cycleaegan", "cyclevaegan")       # train.POOL_ARCHS: optimizer_G and optimizer_D
+SMALL = ("autoencoder", "vae", "doubleae", "doublevae", "cycleae-paired", "cyclevae")
+LARGE = ("aegan", "vaegan", "cycleaegan", "cyclevaegan", "cyclevaegan-paired")
+# the smallest the goldens use; the discriminators' 16 x 16 full-map layer admits nothing below 256
+SIZE = {**{c: 64 for c in SMALL}, **{c: 256 for c in LARGE}}
+# the weight streams of the golden steps
+SYNTH_KEY = {"autoencoder": "ae64", "vae": "vae64", "cyclevaegan": "dp", "doubleae": "dae64", "doublevae": "dve64",
+             "cycleae-paired": "cae64_paired", "cyclevae": "cve64_unpaired", "aegan": "aeg256", "vaegan": "vag256",
+             "cycleaegan": "cag256_unpaired", "cyclevaegan-paired": "cvg256_paired"}
 STEPS = (3, 4, 5)                      # synth batch / eps stream indices (3, 4: the existing two-rank test's)
 # VCG_BUCKET_MB per model: the largest power of two that still cuts every optimizer into >= 3 buckets (asserted).  Autoencoder
 # 245.7 MiB -> 4 buckets, VAE 252.6 MiB -> 4, CycleVAEGAN optimizer_G 505.2 MiB -> 14 and optimizer_D 22.0 MiB -> 3
-BUCKET_MB = {"autoencoder": 64, "vae": 64, "cyclevaegan": 8}
+# DoubleAE 323.7 MiB -> 3, DoubleVAE 337.5 -> 3, CycleAE 491.4 -> 4, CycleVAE 505.2 -> 4; AEGAN optimizer_G 245.7 -> 9 and
+# optimizer_D 11.0 -> 3, VAEGAN 252.6 -> 12 and 11.0 -> 3, CycleAEGAN 491.4 -> 14 and 22.0 -> 3
+BUCKET_MB = {"autoencoder": 64, "vae": 64, "cyclevaegan": 8, "doubleae": 128, "doublevae": 128, "cycleae-paired": 128,
+             "cyclevae": 128, "aegan": 2, "vaegan": 2, "cycleaegan": 8, "cyclevaegan-paired": 8}
 EMA_DECAY = 0.999
 LAMBDA_SSIM = 0.5
 BETA1 = 0.5                            # configure_optimizers' default betas (0.5, 0.999)
@@ -67,7 +78,7 @@ GRAD_BOUND = 2e-2                      # test_two_rank_step_equals_the_big_batch
 #   with every option off (7.2e-3 there: the shards take other launch plans than the batch of two), not something the options add.
 #   Image pool test, step 1 against the batch of two: optimizer_G 1.34e-2 (the existing test's second step: 1.35e-2), optimizer_D
 #   4.2e-7
-JOIN_LIMIT = {"autoencoder": 240.0, "vae": 240.0, "cyclevaegan": 480.0}       # seconds; a healthy run needs a fraction of it
+JOIN_LIMIT = {**{c: 240.0 for c in SMALL}, **{c: 480.0 for c in LARGE}}       # seconds; a healthy run needs a fraction of it
 BUFFERS = ("flat_grad", "flat_param", "exp_avg", "exp_avg_sq", "flat_ema", "clip_state")
 REPLICATED = ("flat_param", "exp_avg", "exp_avg_sq", "flat_ema", "clip_state")
 POOLS = (("DX", "fake_x", "d_fake_x"), ("DY", "fake_y", "d_fake_y"))
@@ -78,30 +89,43 @@ PLANS = {0: {"DX": ([-2], [-1], [0]), "DY": ([-2], [0], [0])},
 
 
 # ------------------------------------------------------------------ shared by the ranks and the one-process runs
-def _make_model(pkg, arch):
-    if arch == "autoencoder":
-        return pkg.Networks.Autoencoder()
-    if arch == "vae":
-        return pkg.Networks.VariationalAutoencoder(latent_dim=64)
-    return pkg.Networks.CycleVAEGAN(latent_dim=64, paired=False)
+def _base(case):
+    return case.split("-")[0]
+
+
+def _make_model(pkg, case):
+    N, paired = pkg.Networks, case.endswith("-paired")
+    return {"autoencoder": lambda: N.Autoencoder(), "vae": lambda: N.VariationalAutoencoder(latent_dim=64),
+            "doubleae": lambda: N.DoubleAutoencoder(), "doublevae": lambda: N.DoubleVariationalAutoencoder(latent_dim=64),
+            "cycleae": lambda: N.CycleAE(paired=paired), "cyclevae": lambda: N.CycleVAE(latent_dim=64, paired=paired),
+            "aegan": lambda: N.AEGAN(), "vaegan": lambda: N.VAEGAN(latent_dim=64),
+            "cycleaegan": lambda: N.CycleAEGAN(paired=paired),
+            "cyclevaegan": lambda: N.CycleVAEGAN(latent_dim=64, paired=paired)}[_base(case)]()
 
 
 def _batch(pkg, arch, step, dev, rows=slice(None)):
     x, y = pkg.synth.batch(2, SIZE[arch], SEED, step=step)
     xb = torch.from_numpy(x[rows]).to(dev)
-    return {"x": xb, "y": xb if arch != "cyclevaegan" else torch.from_numpy(y[rows]).to(dev)}
+    return {"x": xb, "y": xb if arch in ("autoencoder", "vae") else torch.from_numpy(y[rows]).to(dev)}
+
+
+# eps draws of one training step at batch 2, in the reference's call order: doublevae block A, block B; cyclevae G(x), F(G(x)),
+# F(y), G(F(y)); vaegan G(x), G(y); cyclevaegan G(x), G(y), F(G(x)), F(y), F(x), G(F(y)) (unpaired: the identity draws are skipped)
+EPS_DRAWS = {"vae": (1, (2, 64, 4, 4)), "doublevae": (2, (2, 64, 4, 4)), "cyclevae": (4, (2, 64, 4, 4)),
+             "vaegan": (2, (2, 64, 16, 16)), "cyclevaegan": (6, (2, 64, 16, 16))}
 
 
 def _inject_eps(pkg, arch, step, rows=slice(None)):
-    if arch == "autoencoder":
+    if _base(arch) not in EPS_DRAWS:
         return
-    count, shape = (1, (2, 64, 4, 4)) if arch == "vae" else (6, (2, 64, 16, 16))
+    count, shape = EPS_DRAWS[_base(arch)]
     pkg.ops.inject_eps([torch.from_numpy(e[rows]) for e in pkg.synth.eps_list(count, shape, SEED, step=step)])
 
 
-def _configured(pkg, arch, dev, lr, opt_kw, loss_kw, seed=SEED):
+def _configured(pkg, arch, dev, lr, opt_kw, loss_kw, seed=SEED, synth=True):
     model = _make_model(pkg, arch)
-    load_synth(pkg, model, SYNTH_KEY[arch], STEP_BIAS_STD, seed=seed)
+    if synth:                                    # False: the caller loads a recorded state (_restore) before the first step
+        load_synth(pkg, model, SYNTH_KEY[arch], STEP_BIAS_STD, seed=seed)
     model = model.to(dev).train()
     model.configure_optimizers(lr=lr, **opt_kw)
     model.configure_loss(**LAMBDAS, **loss_kw)
@@ -119,11 +143,54 @@ def _record(model, metrics, buffers):
     return rec
 
 
+def _extras(model):
+    """What a step starts from beside the optimizers' flat buffers (_record holds the parameters, both moments and the average as
+    flat_param, exp_avg, exp_avg_sq and flat_ema: model.state_dict()'s parameters and save_optimizer_states()'s moments are
+    views and clones of exactly these, so they are written once): the buffers no optimizer holds (spectral norm's u and v), the
+    step counters, the average's update count, and the sliced Wasserstein term's seed and call counter."""
+    opts = {n: getattr(model, n) for n in model._opt_names}
+    return {"buffers": {k: v.detach().cpu().clone() for k, v in model.named_buffers()},
+            "steps": {n: list(o.steps) for n, o in opts.items()},
+            "ema_updates": {n: getattr(o, "ema_updates", None) for n, o in opts.items()},
+            "swd": model.save_swd_state() if getattr(model, "swd_term", None) is not None else None}
+
+
+def _restore(model, rec):
+    """Put a plain model of the same case into the state a rank recorded (_record with every buffer of BUFFERS, _extras), through
+    the public loaders: load_state_dict, the optimizers' load_state_dict / load_ema_state, load_swd_state."""
+    torch.cuda.synchronize()
+    names = {id(p): n for n, p in model.named_parameters()}
+    opts = {n: getattr(model, n) for n in model._opt_names}
+
+    def views(n, buf):
+        flat = rec[f"{n}.{buf}"]
+        assert flat.numel() == opts[n].total, (n, buf, flat.numel(), opts[n].total)
+        return [flat[o:o + p.numel()].view(p.shape) for p, o in zip(opts[n].params, opts[n].offsets)]
+
+    sd = dict(rec["extras"]["buffers"])
+    for n, opt in opts.items():
+        sd.update({names[id(p)]: v for p, v in zip(opt.params, views(n, "flat_param"))})
+    model.load_state_dict(sd)
+    for n, opt in opts.items():
+        state = {i: {"step": torch.tensor(float(t)), "exp_avg": a, "exp_avg_sq": b}
+                 for i, (t, a, b) in enumerate(zip(rec["extras"]["steps"][n], views(n, "exp_avg"), views(n, "exp_avg_sq"))) if t > 0}
+        group = {k: v for k, v in opt.param_groups[0].items() if k != "params"}
+        group["params"] = list(range(len(opt.params)))
+        opt.load_state_dict({"state": state, "param_groups": [group]})
+        if opt.flat_ema is not None:
+            opt.load_ema_state({"updates": rec["extras"]["ema_updates"][n], "tensors": views(n, "flat_ema")})
+        opt.grad_scale = 1.0
+    if rec["extras"]["swd"] is not None:
+        model.load_swd_state(rec["extras"]["swd"])
+
+
 # ------------------------------------------------------------------ one rank
 def _rank(rank, world, port, cfg):
     """cfg: arch, outdir, tag, lr, opt_kw, loss_kw, from_backward, buffers, ranks_saving, and the scenario switches `diverge`
     (rank 1 loads other weights and runs a forward before the broadcast), `pool`, `nan_steps` (indices of the steps whose input
-    on rank 1 holds one NaN pixel), `steps` (the synth batch / eps stream index of every step)."""
+    on rank 1 holds one NaN pixel), `steps` (the synth batch / eps stream index of every step), `swd` (the sliced Wasserstein
+    term's seed is derived per rank, as train.py does), `state` (every record carries _extras, and one more record, "init",
+    holds what the rank held before its first step)."""
     import importlib
     import torch.distributed as dist
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -143,7 +210,10 @@ def _rank(rank, world, port, cfg):
         opt_kw = dict(cfg["opt_kw"])
         if cfg["pool"]:
             opt_kw.update(pool_size=1, pool_seed=pkg.ops.rank_seed(SEED, rank))      # as train.py derives it
-        model = _configured(pkg, arch, dev, cfg["lr"], opt_kw, cfg["loss_kw"],
+        loss_kw = dict(cfg["loss_kw"])
+        if cfg.get("swd"):
+            loss_kw.update(swd_seed=pkg.ops.rank_seed(SEED, rank) % 2 ** 32)          # as train.py derives it
+        model = _configured(pkg, arch, dev, cfg["lr"], opt_kw, loss_kw,
                             seed=SEED + 1 if cfg["diverge"] and rank == 1 else SEED)
         clock.append(("model", time.monotonic()))
         calls = {}
@@ -161,6 +231,11 @@ def _rank(rank, world, port, cfg):
             pkg.parallel.broadcast_parameters(model)
         clock.append(("broadcast", time.monotonic()))
         save = rank in cfg["ranks_saving"]
+        if cfg.get("state") and save:
+            rec = _record(model, {}, cfg["buffers"])
+            rec["extras"] = _extras(model)
+            torch.save(rec, os.path.join(cfg["outdir"], f"{cfg['tag']}_rank{rank}_init.pt"))
+            del rec
         for i, step in enumerate(cfg["steps"]):
             batch = _batch(pkg, arch, step, dev, slice(rank, rank + 1))
             if i in cfg["nan_steps"] and rank == 1:
@@ -175,6 +250,8 @@ def _rank(rank, world, port, cfg):
             clock.append((f"step{i}", time.monotonic()))
             rec = _record(model, m, cfg["buffers"])
             rec["log"] = list(red.log[n0:])
+            if cfg.get("state"):
+                rec["extras"] = _extras(model)
             if cfg["pool"]:
                 rec["plans"] = {n: list(p.last_plan) for n, p in model.image_pools.items()}
                 rec["drew"] = {n: (p.last_identity, p.last_drew) for n, p in model.image_pools.items()}
@@ -197,10 +274,10 @@ def _rank(rank, world, port, cfg):
 
 
 def _cfg(arch, outdir, tag="dp", lr=LR, opt_kw=None, loss_kw=None, from_backward=True, buffers=BUFFERS, ranks_saving=(0, 1),
-         diverge=False, pool=False, nan_steps=(), steps=STEPS):
+         diverge=False, pool=False, nan_steps=(), steps=STEPS, swd=False, state=False):
     return dict(arch=arch, outdir=str(outdir), tag=tag, lr=lr, opt_kw=opt_kw or {}, loss_kw=loss_kw or {},
                 from_backward=from_backward, buffers=buffers, ranks_saving=ranks_saving, diverge=diverge, pool=pool,
-                nan_steps=tuple(nan_steps), steps=tuple(steps))
+                nan_steps=tuple(nan_steps), steps=tuple(steps), swd=swd, state=state)
 
 
 def _run_two_ranks(cfg):
@@ -282,7 +359,7 @@ def _grad_distance(exchanged, big):
 
 
 def _opt_names(arch):
-    return ("optimizer_G", "optimizer_D") if arch == "cyclevaegan" else ("optimizer",)
+    return ("optimizer_G", "optimizer_D") if _base(arch) in GAN_ARCHS else ("optimizer",)
 
 
 # ------------------------------------------------------------------ 1. clipping, EMA and SSIM on

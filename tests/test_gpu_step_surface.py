@@ -4,7 +4,9 @@ weights' and image pools' state after three steps, and the configure_optimizers 
 
 Each case runs once with every step-level option off and once with every option its architecture accepts on.  The key lists are
 literals: the reference's names in the reference's order (its training_step / validation_step return dicts), then this
-project's own (loss_ssim, the clip metrics).  Values are only required to be finite floats — what they are is the business of the
+project's own (the KL controls' directly after loss_kl, the image terms, loss_swd, the clip metrics).  The "on" run takes the
+option sets from train.py's *_ARCHS tuples: the four image terms, the sliced Wasserstein term, the free-bits floor and the
+annealed KL weight, clipping, the average and the image pools, all at once.  Values are only required to be finite floats — what they are is the business of the
 golden step tests."""
 import importlib
 import inspect
@@ -72,6 +74,8 @@ VALIDATION = {
     ("cyclevaegan", True): CYCLEGAN + ["loss_kl", "loss_identity", "Gx", "Fy"],
     ("cyclevaegan", False): CYCLEGAN + ["loss_kl", "Gx", "Fy"],
 }
+IMAGE_KEYS = ["loss_ssim", "loss_grad", "loss_freq", "loss_msssim"]        # Losses.IMAGE_TERMS' order, then the multi-scale term
+KL_KEYS = ["loss_kl_fb", "kl_active", "kl_weight"]                       # directly after loss_kl; kl_weight in training steps only
 CLIP_ONE = ["grad_norm", "grad_skipped"]
 CLIP_TWO = ["grad_norm_G", "grad_skipped_G", "grad_norm_D", "grad_skipped_D"]
 TENSORS = ("Gx", "Fy")
@@ -98,9 +102,18 @@ def two_optimizers(arch):
 def expected_keys(arch, paired, on):
     trn, val = list(TRAIN[arch, paired]), list(VALIDATION[arch, paired])
     if on:
-        if arch in train.SSIM_ARCHS:             # the structural term follows the model's other losses, the images come last
-            trn.append("loss_ssim")
-            val.insert(val.index("Gx"), "loss_ssim")
+        if arch in train.KL_ARCHS:
+            at = trn.index("loss_kl") + 1
+            trn[at:at] = KL_KEYS
+            at = val.index("loss_kl") + 1
+            val[at:at] = KL_KEYS[:2]
+        if arch in train.SSIM_ARCHS:             # the image terms follow the model's other losses, the images come last
+            trn += IMAGE_KEYS
+            at = val.index("Gx")
+            val[at:at] = IMAGE_KEYS
+        if arch in train.SWD_ARCHS:              # after the image terms; cycleae / cyclevae report it after their images (and loss_trans)
+            trn.append("loss_swd")
+            val.insert(val.index("Gx") if two_optimizers(arch) else len(val), "loss_swd")
         trn += CLIP_TWO if two_optimizers(arch) else CLIP_ONE        # the clip metrics close the training dict
     return trn, val
 
@@ -115,8 +128,13 @@ def make_model(pkg, device, arch, paired, on, synth=True):
         opt_kw = dict(clip_grad_norm=1.0, ema_decay=0.5)
         if arch in train.POOL_ARCHS:
             opt_kw.update(pool_size=2, pool_seed=1)
-        if arch in train.SSIM_ARCHS:
-            loss_kw = dict(lambda_ssim=0.5)
+        if arch in train.SSIM_ARCHS:             # the deepest pyramids run_case's images admit: 64 >> 2 = 16 and 256 >> 4 = 16 >= 11
+            loss_kw.update(lambda_ssim=0.5, lambda_grad=0.5, lambda_freq=0.5, lambda_msssim=0.5, grad_scales=4,
+                           msssim_scales=5 if two_optimizers(arch) else 3)
+        if arch in train.SWD_ARCHS:              # 64 -> 32 -> 16 and 256 -> 128 -> 64: three levels either way
+            loss_kw.update(lambda_swd=0.5, swd_levels=3, swd_seed=1)
+        if arch in train.KL_ARCHS:
+            loss_kw.update(kl_free_bits=0.05, kl_anneal_steps=4, kl_cycles=2, kl_ramp=0.5)
     model.configure_optimizers(lr=LR, **opt_kw)
     model.configure_loss(**LAMBDAS, **loss_kw)
     return model
