@@ -368,6 +368,26 @@ int vcg_fullmap_wgrad(const float* g, const float* x, const float* wsn_k, const 
                       const float* u, const float* v, float* gw_orig_oihw, float* gbias,
                       int N, int C, int KH, int KW, void* ws, size_t ws_bytes, void* stream);
 
+/* The same layer on a map larger than its kernel — Networks.py:248 followed by .view(-1, 1).squeeze(1), Networks.py:269: a valid,
+   stride-1 convolution with one output channel, the patch discriminator the reference becomes above 256 x 256.
+   x (N, H, W, C) NHWC, wsn_k as vcg_sn_prepare writes it ((kh KW + kw) C + c), C % 4 == 0, KH <= H, KW <= W (kernels above
+   16 rows or columns run as tiles of 16); OH = H - KH + 1, OW = W - KW + 1.  fp32 products and sums on the fp32 MFMA, no
+   atomics, every sum in an order fixed by the shapes, and image n's results do not depend on the rest of the batch.
+   ws: vcg_patch_head_workspace(...) bytes (one size for the three directions, a multiple of 16; 0 and vcg_last_error for bad
+   dims or a map row too wide for the on-chip staging, some 400 pixels).  csrc/patch_head.hip. */
+size_t vcg_patch_head_workspace(int N, int H, int W, int C, int KH, int KW);
+/* out[(n OH + oy) OW + ox] = bias[0] + sum_{ky,kx,c} x[n, oy+ky, ox+kx, c] wsn_k[ky, kx, c] (bias may be NULL) — Networks.py:248, :269 */
+int vcg_patch_head_fwd(const float* x, const float* wsn_k, const float* bias, float* out, int N, int H, int W, int C, int KH,
+                       int KW, void* ws, size_t ws_bytes, void* stream);
+/* dx[n, y, x, c] = sum_{oy,ox} g[n, oy, ox] wsn_k[y-oy, x-ox, c]: every element of dx written, none accumulated — the data
+   gradient of Networks.py:248 */
+int vcg_patch_head_dgrad(const float* g, const float* wsn_k, float* dx, int N, int H, int W, int C, int KH, int KW, void* stream);
+/* gk[ky, kx, c] = sum_{n,oy,ox} g[n, oy, ox] x[n, oy+ky, ox+kx, c], then as vcg_fullmap_wgrad: gw_orig_oihw += d(W/sigma)^T gk,
+   gbias[0] += sum of all N OH OW entries of g (gbias may be NULL) — the weight gradient of Networks.py:248 */
+int vcg_patch_head_wgrad(const float* g, const float* x, const float* wsn_k, const float* sigma, const float* u, const float* v,
+                         float* gw_orig_oihw, float* gbias, int N, int H, int W, int C, int KH, int KW, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* Input transforms on the device — the torchvision pipelines of train.py:184-190, 248-262, 309-319 ------------------------- */
 /* RandomHorizontal/VerticalFlip -> RandomResizedCrop(S, BICUBIC) | Resize((S,S)) -> ToTensor for N decoded uint8 HWC images
    packed in `arena`.  params[n][16] (device, int32): source offset lo, hi; source H, W; crop box y0, x0, h, w in

@@ -254,8 +254,9 @@ class VariationalDecoderBlock(nn.Module):
 
 
 class Discriminator(nn.Module):
-    """4x (conv4x4 s2 [+IN] + LeakyReLU 0.2) + spectral-normed 16x16 conv -> one scalar per image
-    (reference Networks.py:240-269)."""
+    """4x (conv4x4 s2 [+IN] + LeakyReLU 0.2) + spectral-normed 16x16 conv, flattened (reference Networks.py:240-269): one
+    logit per image at 256x256, and a patch discriminator above it — (H/16 - 15)(W/16 - 15) logits per image, n-major
+    (ops.head_output_shape).  The losses and the d_*_mean metrics are means over all logits, as the reference's are."""
 
     def __init__(self):
         super().__init__()

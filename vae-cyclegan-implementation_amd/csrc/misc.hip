@@ -694,6 +694,15 @@ extern "C" int vcg_fullmap_wgrad(const float* g, const float* x, const float* ws
   VCG_LAUNCH_CHECK("vcg_fullmap_wgrad");
   return 0;
 }
+// the same stage for patch_head.hip: gk (kh, kw, c order) and `nparts` partial dots with wsn_k in, the spectral-norm Jacobian, the
+// OIHW permutation and gbias += sum of g[0 .. Ng) out — one statement of the mathematics for both heads
+int vcg_sn_wgrad_finish(const float* gk, const float* part, int nparts, const float* sigma, const float* u, const float* v,
+                        const float* g, int Ng, float* gw_orig_oihw, float* gbias, int C, int KK, hipStream_t st) {
+  hipLaunchKernelGGL(k_fullmap_wgrad2, dim3(kFmBlocks), dim3(256), 0, st, gk, part, nparts, sigma, u, v, g, gw_orig_oihw, gbias,
+                     Ng, C, KK);
+  VCG_LAUNCH_CHECK("vcg_sn_wgrad_finish");
+  return 0;
+}
 
 // ---------------------------------------------------------------- Adam
 // torch.optim.adam._single_tensor_adam, fp32, amsgrad=False, weight_decay=0, maximize=False:

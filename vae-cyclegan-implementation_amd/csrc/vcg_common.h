@@ -310,6 +310,9 @@ struct VcgInStatsOut {
   int HW;                 // pixels per image the partials cover
   float eps;
 };
+// misc.hip: the last stage of the spectral-normed head's weight gradient (k_fullmap_wgrad2), shared with patch_head.hip
+int vcg_sn_wgrad_finish(const float* gk, const float* part, int nparts, const float* sigma, const float* u, const float* v,
+                        const float* g, int Ng, float* gw_orig_oihw, float* gbias, int C, int KK, hipStream_t st);
 int vcg_in_stats_pass(const float* t, float* mean, float* rstd, int N, int HW, int C, float eps, void* ws, size_t ws_bytes, hipStream_t st);
 
 // geometry derived from the int32[16] conv descriptor

@@ -1561,9 +1561,35 @@ def weighted_sum(terms, weights):
     return _LinCombFn.apply(list(weights), *terms)
 
 
-# ------------------------------------------------------------------ spectral-normed full-map conv
+# ------------------------------------------------------------------ spectral-normed discriminator head
+HEAD_STRIDE = 16    # the discriminator body halves the image four times before the head (Networks.py:241-247)
+
+
+def head_output_shape(image_h, image_w=None, kernel=(16, 16)):
+    """(OH, OW) of the discriminator head's logits for an image of image_h x image_w pixels (square when image_w is None): the
+    body's four stride-2 layers leave a map of image / 16, and the head is a valid, stride-1 convolution over it
+    (Networks.py:248) — (1, 1) at 256 x 256, (17, 17) at 512 x 512.  Raises for a size the head does not accept."""
+    image_w = image_h if image_w is None else image_w
+    kh, kw = kernel
+    for side in (image_h, image_w):
+        if int(side) != side or side % HEAD_STRIDE:
+            raise RuntimeError(f"discriminator image sizes must be multiples of {HEAD_STRIDE}; got {image_h}x{image_w}")
+    h, w = int(image_h) // HEAD_STRIDE, int(image_w) // HEAD_STRIDE
+    if h < kh or w < kw:
+        raise RuntimeError(_head_too_small(h, w, kh, kw))
+    return h - kh + 1, w - kw + 1
+
+
+def _head_too_small(h, w, kh, kw, c=None):
+    what = f"{h}x{w}" if c is None else f"{c}x{h}x{w}"
+    return (f"discriminator head: a {what} map is smaller than the {kh}x{kw} kernel; the smallest accepted image is "
+            f"{HEAD_STRIDE * kh}x{HEAD_STRIDE * kw} (the reference's Conv2d(512, 1, 16, padding=0) fails below it too)")
+
+
 class _FullMapSNFn(torch.autograd.Function):
-    """spectral_norm(nn.Conv2d(C, 1, k, padding=0)) on a k x k map -> (N,)  (Networks.py:248, :269)."""
+    """spectral_norm(nn.Conv2d(C, 1, k, padding=0)) followed by .view(-1, 1).squeeze(1) -> (N OH OW,)  (Networks.py:248, :269).
+    A k x k map (256 x 256 images) is one dot product per image, the vcg_fullmap_* kernels; a larger map is the sliding
+    (patch) convolution of the vcg_patch_head_* kernels.  The spectral-norm state is handled the same way for both."""
 
     @staticmethod
     def forward(ctx, x, weight_orig, bias, u, v, training, wparam, bparam):
@@ -1571,20 +1597,33 @@ class _FullMapSNFn(torch.autograd.Function):
         xp = as_phys(x)
         n, h, w, c = xp.shape
         _, cw, kh, kw = weight_orig.shape
-        if (h, w) != (kh, kw) or c != cw:
-            raise RuntimeError(f"discriminator head expects a {cw}x{kh}x{kw} map (256x256 input images); got {c}x{h}x{w}")
+        if c != cw:
+            raise RuntimeError(f"discriminator head expects {cw} channels; got a {c}x{h}x{w} map")
+        if h < kh or w < kw:
+            raise RuntimeError(_head_too_small(h, w, kh, kw, c))
         dev = x.device
         k = c * kh * kw
+        patch = (h, w) != (kh, kw)
+        if patch:
+            ws_bytes = lib.vcg_patch_head_workspace(n, h, w, c, kh, kw)
+            if not ws_bytes:
+                _native.check(-1, "vcg_patch_head_workspace")
         sigma = torch.empty(1, dtype=torch.float32, device=dev)
         wsn = torch.empty(k, dtype=torch.float32, device=dev)
         wo = weight_orig.detach().contiguous()
         ws = workspace(64, dev)
         _native.check(lib.vcg_sn_prepare(_ptr(wo), _ptr(u), _ptr(v), _ptr(sigma), _ptr(wsn), c, kh, kw, int(training),
                                          _ptr(ws), 64, _stream()), "vcg_sn_prepare")
-        out = torch.empty(n, dtype=torch.float32, device=dev)
-        _native.check(lib.vcg_fullmap_fwd(_ptr(xp), _ptr(wsn), _ptr(bias), _ptr(out), n, k, _stream()), "vcg_fullmap_fwd")
+        if patch:
+            out = torch.empty(n * (h - kh + 1) * (w - kw + 1), dtype=torch.float32, device=dev)
+            ws = workspace(ws_bytes, dev)
+            _native.check(lib.vcg_patch_head_fwd(_ptr(xp), _ptr(wsn), _ptr(bias), _ptr(out), n, h, w, c, kh, kw, _ptr(ws),
+                                                 ws.numel() * 4, _stream()), "vcg_patch_head_fwd")
+        else:
+            out = torch.empty(n, dtype=torch.float32, device=dev)
+            _native.check(lib.vcg_fullmap_fwd(_ptr(xp), _ptr(wsn), _ptr(bias), _ptr(out), n, k, _stream()), "vcg_fullmap_fwd")
         ctx.save_for_backward(xp, wsn, sigma, u.clone(), v.clone())
-        ctx.dims = (n, c, kh, kw)
+        ctx.dims = (n, h, w, c, kh, kw)
         ctx.wparam, ctx.bparam = wparam, bparam
         return out
 
@@ -1592,8 +1631,9 @@ class _FullMapSNFn(torch.autograd.Function):
     def backward(ctx, g):
         lib = _native.lib()
         xp, wsn, sigma, u, v = ctx.saved_tensors
-        n, c, kh, kw = ctx.dims
+        n, h, w, c, kh, kw = ctx.dims
         k = c * kh * kw
+        patch = (h, w) != (kh, kw)
         g = g.contiguous()
         dev = g.device
         wparam, bparam = ctx.wparam, ctx.bparam
@@ -1604,20 +1644,31 @@ class _FullMapSNFn(torch.autograd.Function):
         if want_w or bias_alone:
             gw = _grad_buffer(wparam) if want_w else torch.zeros_like(wparam, memory_format=torch.contiguous_format)
             gb = _grad_buffer(bparam) if (bparam is not None and bparam.requires_grad) else None
-            ws = workspace((k + 256) * 4, dev)
-            _native.check(lib.vcg_fullmap_wgrad(_ptr(g), _ptr(xp), _ptr(wsn), _ptr(sigma), _ptr(u), _ptr(v), _ptr(gw),
-                                                _ptr(gb), n, c, kh, kw, _ptr(ws), ws.numel() * 4, _stream()), "vcg_fullmap_wgrad")
+            if patch:
+                ws = workspace(lib.vcg_patch_head_workspace(n, h, w, c, kh, kw), dev)
+                _native.check(lib.vcg_patch_head_wgrad(_ptr(g), _ptr(xp), _ptr(wsn), _ptr(sigma), _ptr(u), _ptr(v), _ptr(gw),
+                                                       _ptr(gb), n, h, w, c, kh, kw, _ptr(ws), ws.numel() * 4, _stream()),
+                              "vcg_patch_head_wgrad")
+            else:
+                ws = workspace((k + 256) * 4, dev)
+                _native.check(lib.vcg_fullmap_wgrad(_ptr(g), _ptr(xp), _ptr(wsn), _ptr(sigma), _ptr(u), _ptr(v), _ptr(gw),
+                                                    _ptr(gb), n, c, kh, kw, _ptr(ws), ws.numel() * 4, _stream()), "vcg_fullmap_wgrad")
             if GRAD_READY_HOOK[0] is not None:
                 GRAD_READY_HOOK[0](wparam if want_w else None, bparam, torch.cuda.current_stream(dev))
         dx = None
         if ctx.needs_input_grad[0]:
             dxp = torch.empty_like(xp)
-            _native.check(lib.vcg_fullmap_dgrad(_ptr(g), _ptr(wsn), _ptr(dxp), n, k, _stream()), "vcg_fullmap_dgrad")
+            if patch:
+                _native.check(lib.vcg_patch_head_dgrad(_ptr(g), _ptr(wsn), _ptr(dxp), n, h, w, c, kh, kw, _stream()),
+                              "vcg_patch_head_dgrad")
+            else:
+                _native.check(lib.vcg_fullmap_dgrad(_ptr(g), _ptr(wsn), _ptr(dxp), n, k, _stream()), "vcg_fullmap_dgrad")
             dx = logical_of(dxp, c)
         return dx, None, None, None, None, None, None, None
 
 
 def fullmap_sn_conv(x, weight_orig, bias, u, v, training):
+    """The discriminator head on an NHWC map of at least the kernel's size -> logits (N OH OW,), n-major, then oy, then ox."""
     _require_gpu(x, "fullmap_sn_conv")
     return _FullMapSNFn.apply(x, weight_orig, bias, u, v, training, weight_orig, bias)
 

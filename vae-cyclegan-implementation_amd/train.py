@@ -277,6 +277,18 @@ def ema_decay_value(text):
 POOL_ARCHS = ("aegan", "vaegan", "cycleaegan", "cyclevaegan")       # the architectures with a discriminator
 
 
+def check_image_size(architecture, image_size):
+    """--image_size for the architectures with a discriminator: a multiple of 16 (the body halves the image four times) and at
+    least 256 (the head's 16x16 kernel on the map of image / 16; ops.head_output_shape).  The other architectures are not
+    looked at here.  Raises ValueError before the first step."""
+    if ALIASES.get(architecture, architecture) not in POOL_ARCHS:
+        return
+    try:
+        ops.head_output_shape(image_size, image_size)
+    except RuntimeError as e:
+        raise ValueError(f"--image_size {image_size} is not usable with {architecture}: {e}") from None
+
+
 def pool_size_value(text):
     """argparse type of --pool_size: an integer >= 0 (0: off)."""
     try:
@@ -450,6 +462,7 @@ def main(args):
     if isinstance(msssim_scales, bool) or msssim_scales not in (1, 2, 3, 4, 5):
         raise ValueError(f"--msssim_scales must be 1, 2, 3, 4 or 5, got {msssim_scales}")
     image_size = getattr(args, "image_size", 256)
+    check_image_size(args.architecture, image_size)
     if lambda_msssim != 0.0 and ops.msssim_max_scales(image_size, image_size) < msssim_scales:
         usable = ops.msssim_max_scales(image_size, image_size)
         raise ValueError(f"--image_size {image_size} is too small for --msssim_scales {msssim_scales}: the coarsest level, "
