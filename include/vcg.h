@@ -239,6 +239,28 @@ int vcg_l1_bwd(const float* a, const float* b, const float* gout, float* ga, flo
 /* nn.MSELoss vs a constant — Losses.py:78-83,97-102: out[0]=mean((d-c)^2), out[1]=mean(d) */
 int vcg_mse_const_fwd(const float* d, float target, float* out, size_t n, void* stream);
 int vcg_mse_const_bwd(const float* d, float target, const float* gout, float* gd, size_t n, void* stream);
+/* The adversarial terms of one discriminator's real / fake logit pair under a selectable objective (new: the reference has the
+   LSGAN of vcg_mse_const_* alone, which stays the default path).  real, fake: dense fp32 logits, n_real and n_fake of them; a side
+   is present with a pointer and a count or absent with null and 0, not both absent.  smooth: the one-sided label smoothing s of
+   the discriminator's real term, finite, 0 <= s < 0.5, and 0 with the hinge.  Each term is the mean over its tensor of, with
+   sp(t) = max(t, 0) + log1p(exp(-|t|)):
+     objective               D real                     D fake          G real   G fake
+     VCG_GAN_LSGAN           (z - (1 - s))^2            z^2             z^2      (z - 1)^2
+     VCG_GAN_HINGE           max(0, 1 - z)              max(0, 1 + z)   z        -z
+     VCG_GAN_LOGISTIC        (1 - s) sp(-z) + s sp(z)   sp(z)           sp(z)    sp(-z)
+     out[0..6) = g_real, g_fake, d_real, d_fake, mean(real), mean(fake); the slots of an absent side are written as 0
+   One launch, workgroup 0 on `real` and workgroup 1 on `fake`: summands and sums in double, a fixed combination order, no
+   atomics, one rounding to fp32 at the store.  A NaN logit gives NaN terms; an infinite one the limit.  csrc/gan_terms.hip. */
+enum { VCG_GAN_LSGAN = 0, VCG_GAN_HINGE = 1, VCG_GAN_LOGISTIC = 2 };
+int vcg_gan_terms_fwd(const float* real, size_t n_real, const float* fake, size_t n_fake, int objective, double smooth,
+                      float* out, void* stream);
+/* g_out: a host table of four device scalars, the upstream gradients of g_real, g_fake, d_real, d_fake; a null entry = that term
+   is not differentiated (the generator and the discriminator phase of a step each set their own).  One elementwise launch:
+     g_real[i] = (g_out[0] G'(real[i]) + g_out[2] D'(real[i])) / n_real;  g_fake[i] likewise from g_out[1], g_out[3], n_fake
+   evaluated in double and rounded once; the hinge's derivative at its kink (z = 1 real, z = -1 fake) is 0.  A present side's
+   buffer is written whole (zeros where both its entries are null); an absent side's may be null. */
+int vcg_gan_terms_bwd(const float* real, size_t n_real, const float* fake, size_t n_fake, int objective, double smooth,
+                      const float* const* g_out, float* g_real, float* g_fake, void* stream);
 /* KLDivergenceLoss — Losses.py:115-121                                       */
 int vcg_kl_fwd(const float* mu, const float* lv, float* out, size_t n,
                void* ws, size_t ws_bytes, void* stream);

@@ -161,21 +161,62 @@ class SlicedWassersteinLoss(nn.Module):
         self.seed, self.step = int(state["seed"]), int(state["step"])
 
 
+class GanObjective(NamedTuple):
+    """The adversarial objective of the GAN models: `objective`, one of ops.GAN_OBJECTIVES — the reference's least squares, the
+    hinge (Lim & Ye 2017) or the non-saturating logistic loss (Goodfellow et al. 2014) — and `label_smooth`, the one-sided label
+    smoothing of the discriminator's real term (Salimans et al. 2016).  The default is the reference's objective on the
+    reference's kernels (ops.mse_const); anything else goes through ops.gan_terms."""
+    objective: str = "lsgan"
+    label_smooth: float = 0.0
+
+
+LSGAN = GanObjective()
+
+
+def gan_objective(objective="lsgan", label_smooth=0.0):
+    """The validated GanObjective of a loss constructor or a configure_loss call."""
+    if not isinstance(objective, str) or objective not in ops.GAN_OBJECTIVES:
+        raise ValueError(f"objective must be one of {', '.join(ops.GAN_OBJECTIVES)}, got {objective!r}")
+    if (isinstance(label_smooth, bool) or not isinstance(label_smooth, (int, float)) or not math.isfinite(label_smooth)
+            or not 0.0 <= label_smooth < 0.5):
+        raise ValueError(f"label_smooth must be a finite number in [0, 0.5), got {label_smooth!r}")
+    if objective == "hinge" and label_smooth != 0.0:
+        raise ValueError(f"label_smooth={label_smooth!r}: the hinge objective has no target to smooth; use lsgan or logistic")
+    return GanObjective(objective, float(label_smooth))
+
+
 class GANLossGenerator(nn.Module):
-    """LSGAN generator terms: real -> 0, fake -> 1; returns (total, real, fake)  (reference Losses.py:67-83)."""
+    """Generator terms, returns (total, real, fake).  Default: LSGAN, real -> 0, fake -> 1 (reference Losses.py:67-83); another
+    `objective` of ops.GAN_OBJECTIVES: that objective's generator terms from ops.gan_terms (`label_smooth` shapes the
+    discriminator's real term alone; it is taken so that both classes are built from the same arguments)."""
+
+    def __init__(self, objective="lsgan", label_smooth=0.0):
+        super().__init__()
+        self.config = gan_objective(objective, label_smooth)
 
     def forward(self, D_real, D_fake):
-        real_loss, _ = ops.mse_const(D_real, 0.0)
-        fake_loss, _ = ops.mse_const(D_fake, 1.0)
+        if self.config == LSGAN:
+            real_loss, _ = ops.mse_const(D_real, 0.0)
+            fake_loss, _ = ops.mse_const(D_fake, 1.0)
+        else:
+            real_loss, fake_loss = ops.gan_terms(D_real, D_fake, *self.config)[0:2]
         return ops.weighted_sum([real_loss, fake_loss], [1.0, 1.0]), real_loss, fake_loss
 
 
 class GANLossDiscriminator(nn.Module):
-    """LSGAN discriminator terms: real -> 1, fake -> 0; returns (total, real, fake)  (reference Losses.py:86-102)."""
+    """Discriminator terms, returns (total, real, fake).  Default: LSGAN, real -> 1, fake -> 0 (reference Losses.py:86-102);
+    otherwise the discriminator terms of `objective` with the real term's target smoothed by `label_smooth`, from ops.gan_terms."""
+
+    def __init__(self, objective="lsgan", label_smooth=0.0):
+        super().__init__()
+        self.config = gan_objective(objective, label_smooth)
 
     def forward(self, D_real, D_fake):
-        real_loss, _ = ops.mse_const(D_real, 1.0)
-        fake_loss, _ = ops.mse_const(D_fake, 0.0)
+        if self.config == LSGAN:
+            real_loss, _ = ops.mse_const(D_real, 1.0)
+            fake_loss, _ = ops.mse_const(D_fake, 0.0)
+        else:
+            real_loss, fake_loss = ops.gan_terms(D_real, D_fake, *self.config)[2:4]
         return ops.weighted_sum([real_loss, fake_loss], [1.0, 1.0]), real_loss, fake_loss
 
 

@@ -20,8 +20,8 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .Losses import (IMAGE_TERMS, CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss, KLDivergenceLoss,
-                     MultiScaleStructuralLoss, SlicedWassersteinLoss, TranslationLoss)
+from .Losses import (IMAGE_TERMS, LSGAN, CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss,
+                     KLDivergenceLoss, MultiScaleStructuralLoss, SlicedWassersteinLoss, TranslationLoss, gan_objective)
 from .image_pool import ImagePool, pool_seed as _pool_seed
 from .optim import FusedAdam, kl_weight_at
 
@@ -594,6 +594,52 @@ def _kl_host(model, training):
     return {"kl_weight": float(model.kl_weight_used)} if training and control.anneal_steps else {}
 
 
+GAN_MODELS = "aegan, vaegan, cycleaegan and cyclevaegan"      # the models with a discriminator and an adversarial objective
+
+
+def _gan_objective(kwargs):
+    """The validated Losses.GanObjective of a configure_loss call (gan_objective, gan_label_smooth)."""
+    return gan_objective(kwargs.get("gan_objective", "lsgan"), kwargs.get("gan_label_smooth", 0.0))
+
+
+def _refuse_gan_objective(model, kwargs):
+    """configure_loss of the models without a discriminator takes the keywords so that one call fits every architecture: the
+    defaults are ignored."""
+    config = _gan_objective(kwargs)
+    if config != LSGAN:
+        given = ", ".join(f"gan_{k}={v!r}" for k, v, d in zip(config._fields, config, LSGAN) if v != d)
+        raise ValueError(f"{given}: {type(model).__name__} has no discriminator and no adversarial objective ({GAN_MODELS} have)")
+
+
+def _configure_gan(model, kwargs):
+    """-> the (generator, discriminator) loss modules of a GAN model's configure_loss; leaves `gan_objective` on the model."""
+    model.gan_objective = _gan_objective(kwargs)
+    return GANLossGenerator(*model.gan_objective), GANLossDiscriminator(*model.gan_objective)
+
+
+class _GanTerms:
+    """The adversarial terms of one discriminator's logits on real and on generated images (either may be None) under a model's
+    objective, each a (term, logit mean) pair.  LSGAN without smoothing: every term is its own ops.mse_const call, issued where
+    the step asks for it — call for call and launch for launch the step as it was before the objective could be chosen.  Any
+    other objective: ONE ops.gan_terms call here serves all four terms and both means."""
+
+    def __init__(self, config, real, fake):
+        self.real, self.fake = real, fake
+        self.fused = None if config == LSGAN else ops.gan_terms(real, fake, *config)
+
+    def g_real(self):
+        return ops.mse_const(self.real, 0.0) if self.fused is None else (self.fused[0], self.fused[4])
+
+    def g_fake(self):
+        return ops.mse_const(self.fake, 1.0) if self.fused is None else (self.fused[1], self.fused[5])
+
+    def d_real(self):
+        return ops.mse_const(self.real, 1.0) if self.fused is None else (self.fused[2], self.fused[4])
+
+    def d_fake(self):
+        return ops.mse_const(self.fake, 0.0) if self.fused is None else (self.fused[3], self.fused[5])
+
+
 def _backward_and_step(loss, optimizer, reducer):
     """zero_grad -> backward -> [data-parallel gradient exchange, its buckets launched from inside the backward] -> step."""
     optimizer.zero_grad()
@@ -714,6 +760,7 @@ class _GanMixin(_PoolMixin, _OptimizerStatesMixin):
     """The models with discriminators (`_discriminators`, trained by optimizer_D) beside their generators (`_generators`,
     optimizer_G): the optimizer pair and the alternating G then D update."""
     _opt_names = ("optimizer_G", "optimizer_D")
+    gan_objective = LSGAN                        # configure_loss(gan_objective=..., gan_label_smooth=...) replaces it
 
     def _gan_optimizers(self, lr, betas, clip_grad_norm, ema_decay, pool_size, pool_seed):
         # pool_size > 0: an image history pool of that many images per discriminator (DX pools F(y), DY pools G(x), D pools G(x)),
@@ -810,6 +857,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
         _refuse_kl_control(self, kwargs)
+        _refuse_gan_objective(self, kwargs)
         self.loss_fn = TranslationLoss()
         self.image_terms = _image_terms(kwargs)
 
@@ -914,6 +962,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
 
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
+        _refuse_gan_objective(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
         self.loss_kl_fn = _configure_kl(self, kwargs)
         self.image_terms = _image_terms(kwargs)
@@ -1113,8 +1162,7 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
 
     def configure_loss(self, **kwargs):
         self.loss_cycle = CycleConsistencyLoss()
-        self.loss_gan_gen = GANLossGenerator()
-        self.loss_gan_disc = GANLossDiscriminator()
+        self.loss_gan_gen, self.loss_gan_disc = _configure_gan(self, kwargs)
         if self.paired:
             self.loss_identity = IdentityLoss()
         if self._variational:
@@ -1167,10 +1215,11 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
 
         t = {}
         t["loss_cycle"] = self.loss_cycle(x, y, FGx, GFy)
-        t["loss_gan_g_x_fake"], t["d_x_fake_mean"] = ops.mse_const(DXFy, 1.0)
-        t["loss_gan_g_y_fake"], t["d_y_fake_mean"] = ops.mse_const(DYGx, 1.0)
-        t["loss_gan_g_x_real"], t["d_x_real_mean"] = ops.mse_const(DXx, 0.0)
-        t["loss_gan_g_y_real"], t["d_y_real_mean"] = ops.mse_const(DYy, 0.0)
+        gan_x, gan_y = _GanTerms(self.gan_objective, DXx, DXFy), _GanTerms(self.gan_objective, DYy, DYGx)
+        t["loss_gan_g_x_fake"], t["d_x_fake_mean"] = gan_x.g_fake()
+        t["loss_gan_g_y_fake"], t["d_y_fake_mean"] = gan_y.g_fake()
+        t["loss_gan_g_x_real"], t["d_x_real_mean"] = gan_x.g_real()
+        t["loss_gan_g_y_real"], t["d_y_real_mean"] = gan_y.g_real()
         t["loss_gan_g"] = ops.weighted_sum([t[k] for k in self._GAN_G_TERMS], [1.0] * len(self._GAN_G_TERMS))
         terms, weights = [t["loss_cycle"], t["loss_gan_g"]], [self.lambda_cycle, self.lambda_gan]
         if self._variational:
@@ -1191,10 +1240,10 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
         self._add_swd(t, terms, weights, Gx, Fy, x, y)     # the translated batches against the other domain's: needs no pairing
         t["G_loss"] = ops.weighted_sum(terms, weights)
         # discriminator objective on the SAME discriminator outputs (reference :2038-2040)
-        t["D_loss_x_real"], _ = ops.mse_const(DXx, 1.0)
-        t["D_loss_x_fake"], _ = ops.mse_const(DXFy, 0.0)
-        t["D_loss_y_real"], _ = ops.mse_const(DYy, 1.0)
-        t["D_loss_y_fake"], _ = ops.mse_const(DYGx, 0.0)
+        t["D_loss_x_real"], _ = gan_x.d_real()
+        t["D_loss_x_fake"], _ = gan_x.d_fake()
+        t["D_loss_y_real"], _ = gan_y.d_real()
+        t["D_loss_y_fake"], _ = gan_y.d_fake()
         t["D_loss"] = ops.weighted_sum([t["D_loss_x_real"], t["D_loss_x_fake"], t["D_loss_y_real"], t["D_loss_y_fake"]],
                                        [1.0] * 4)
         return t, Gx, Fy
@@ -1220,9 +1269,9 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
         shown_x, extra_x = self._shown_to("DX", fake_x)
         shown_y, extra_y = self._shown_to("DY", fake_y)
         if extra_x:
-            t["D_loss_x_fake"], _ = ops.mse_const(self.DX(shown_x), 0.0)
+            t["D_loss_x_fake"], _ = _GanTerms(self.gan_objective, None, self.DX(shown_x)).d_fake()
         if extra_y:
-            t["D_loss_y_fake"], _ = ops.mse_const(self.DY(shown_y), 0.0)
+            t["D_loss_y_fake"], _ = _GanTerms(self.gan_objective, None, self.DY(shown_y)).d_fake()
         if extra_x or extra_y:
             t["D_loss"] = ops.weighted_sum([t["D_loss_x_real"], t["D_loss_x_fake"], t["D_loss_y_real"], t["D_loss_y_fake"]],
                                            [1.0] * 4)
@@ -1368,6 +1417,7 @@ class CycleAE(_CycleNoGAN):
         self._init_common(paired)
 
     def configure_loss(self, **kwargs):
+        _refuse_gan_objective(self, kwargs)
         self.loss_cycle = CycleConsistencyLoss()
         if self.paired:
             self.loss_trans = TranslationLoss()
@@ -1388,6 +1438,7 @@ class CycleVAE(_CycleNoGAN):
         self._init_common(paired)
 
     def configure_loss(self, **kwargs):
+        _refuse_gan_objective(self, kwargs)
         self.loss_cycle = CycleConsistencyLoss()
         if self.paired:
             self.loss_trans = TranslationLoss()
@@ -1466,6 +1517,7 @@ class DoubleAutoencoder(_DoubleStep):
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
         _refuse_kl_control(self, kwargs)
+        _refuse_gan_objective(self, kwargs)
         self.loss_fn = TranslationLoss()
 
     def _check_configured(self, need_opt=True):
@@ -1569,6 +1621,7 @@ class DoubleVariationalAutoencoder(_DoubleStep):
 
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
+        _refuse_gan_objective(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
         self.loss_kl_fn = _configure_kl(self, kwargs)
 
@@ -1600,13 +1653,15 @@ class _SingleGAN(_GanMixin, nn.Module):
         return self._gan_optimizers(lr, betas, clip_grad_norm, ema_decay, pool_size, pool_seed)
 
     def _gan_terms(self, t, DGx, Dy):
-        """LSGAN terms on one discriminator pass: generator (real -> 0, fake -> 1, Losses.py:67-83) and discriminator
-        (real -> 1, fake -> 0, :86-102) objectives, plus the output means AEGAN logs."""
-        t["gan_g_real"], t["d_y_mean"] = ops.mse_const(Dy, 0.0)
-        t["gan_g_fake"], t["d_gx_mean"] = ops.mse_const(DGx, 1.0)
+        """The adversarial terms on one discriminator pass under the model's objective (_GanTerms) — by default LSGAN: generator
+        (real -> 0, fake -> 1, Losses.py:67-83) and discriminator (real -> 1, fake -> 0, :86-102) objectives —, plus the output
+        means AEGAN logs."""
+        gan = _GanTerms(self.gan_objective, Dy, DGx)
+        t["gan_g_real"], t["d_y_mean"] = gan.g_real()
+        t["gan_g_fake"], t["d_gx_mean"] = gan.g_fake()
         t["gan_g"] = ops.weighted_sum([t["gan_g_real"], t["gan_g_fake"]], [1.0, 1.0])
-        t["D_loss_real"], _ = ops.mse_const(Dy, 1.0)
-        t["D_loss_fake"], _ = ops.mse_const(DGx, 0.0)
+        t["D_loss_real"], _ = gan.d_real()
+        t["D_loss_fake"], _ = gan.d_fake()
         t["D_loss"] = ops.weighted_sum([t["D_loss_real"], t["D_loss_fake"]], [1.0, 1.0])
 
     def _pooled_d_terms(self, t, Gx):
@@ -1615,7 +1670,7 @@ class _SingleGAN(_GanMixin, nn.Module):
         fake = Gx.detach()
         shown, extra = self._shown_to("D", fake)
         if extra:
-            t["D_loss_fake"], _ = ops.mse_const(self.D(shown), 0.0)
+            t["D_loss_fake"], _ = _GanTerms(self.gan_objective, None, self.D(shown)).d_fake()
             t["D_loss"] = ops.weighted_sum([t["D_loss_real"], t["D_loss_fake"]], [1.0, 1.0])
         if self.debug_mode:
             self._debug_store().update(fake=fake, d_fake=shown)
@@ -1673,8 +1728,7 @@ class AEGAN(_SingleGAN):
         _refuse_swd(self, kwargs)
         _refuse_kl_control(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
-        self.loss_gan_gen_fn = GANLossGenerator()
-        self.loss_gan_disc_fn = GANLossDiscriminator()
+        self.loss_gan_gen_fn, self.loss_gan_disc_fn = _configure_gan(self, kwargs)
         self.loss_identity_fn = TranslationLoss()
         self.lambda_gan = kwargs.get("lambda_gan", 1.0)
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
@@ -1733,8 +1787,7 @@ class VAEGAN(_SingleGAN):
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
         self.translation_loss = TranslationLoss()
-        self.gan_loss_gen = GANLossGenerator()
-        self.gan_loss_disc = GANLossDiscriminator()
+        self.gan_loss_gen, self.gan_loss_disc = _configure_gan(self, kwargs)
         self.identity_loss = TranslationLoss()
         self.kl_loss = _configure_kl(self, kwargs)
         self.lambda_gan = kwargs.get("lambda_gan", 1.0)

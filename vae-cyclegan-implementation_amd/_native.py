@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # VCG_LIBVCG: load another build of the same sources (A/B runs of kernel variants, tools/); the default is the in-tree library
 LIB_PATH = os.environ.get("VCG_LIBVCG") or os.path.join(_HERE, "libvcg.so")
-SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip", "swd_loss.hip", "msssim_loss.hip", "kl_free_bits.hip", "patch_head.hip"]
+SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip", "swd_loss.hip", "msssim_loss.hip", "kl_free_bits.hip", "patch_head.hip", "gan_terms.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vcg.h")
 
 _c = ctypes
@@ -90,6 +90,8 @@ SIGNATURES = {
     "vcg_freq_loss_bwd": (_I, [_P, _Z, _P, _P, _I, _I, _I, _F, _P, _Z, _P]),
     "vcg_mse_const_fwd": (_I, [_P, _F, _P, _Z, _P]),
     "vcg_mse_const_bwd": (_I, [_P, _F, _P, _P, _Z, _P]),
+    "vcg_gan_terms_fwd": (_I, [_P, _Z, _P, _Z, _I, _D, _P, _P]),
+    "vcg_gan_terms_bwd": (_I, [_P, _Z, _P, _Z, _I, _D, _c.POINTER(_P), _P, _P, _P]),
     "vcg_kl_fwd": (_I, [_P, _P, _P, _Z, _P, _Z, _P]),
     "vcg_kl_bwd": (_I, [_P, _P, _P, _P, _P, _Z, _P]),
     "vcg_kl_fb_workspace": (_Z, [_Z, _I]),

@@ -1416,6 +1416,87 @@ def mse_const(d, target):
     return _MseConstFn.apply(d, target)
 
 
+GAN_OBJECTIVES = ("lsgan", "hinge", "logistic")      # the index is the library's VCG_GAN_* code
+
+
+def _dense_logits(t, what):
+    if t is None:
+        return None
+    _require_gpu(t, what)
+    if t.numel() == 0:
+        raise RuntimeError(f"{what}: empty logit tensor of shape {tuple(t.shape)}")
+    return t.contiguous()
+
+
+class _GanTermsFn(torch.autograd.Function):
+    """The six adversarial scalars of one discriminator's (real, fake) logits (csrc/gan_terms.hip): one launch forward, one
+    backward per phase of the step.  A side without an upstream gradient gets None, so autograd does not walk its discriminator
+    pass: VAEGAN's D phase (the real term alone) and the generator phase (the fake terms alone) cost what they do under LSGAN."""
+
+    @staticmethod
+    def forward(ctx, real, fake, code, smooth):
+        rc, fc = _dense_logits(real, "gan_terms"), _dense_logits(fake, "gan_terms")
+        dev = (rc if rc is not None else fc).device
+        out = torch.empty(6, dtype=torch.float32, device=dev)
+        _call("vcg_gan_terms_fwd", _ptr(rc), 0 if rc is None else rc.numel(), _ptr(fc), 0 if fc is None else fc.numel(),
+              code, smooth, _ptr(out), _stream())
+        ctx.sides = (rc is not None, fc is not None)
+        ctx.save_for_backward(*[t for t in (rc, fc) if t is not None])
+        ctx.call = (code, smooth)
+        ctx.set_materialize_grads(False)
+        terms = tuple(out[i] for i in range(6))
+        ctx.mark_non_differentiable(terms[4], terms[5])
+        return terms
+
+    @staticmethod
+    def backward(ctx, g_g_real, g_g_fake, g_d_real, g_d_fake, _g_mean_real, _g_mean_fake):
+        if torch.is_grad_enabled():               # create_graph=True: a gradient penalty or the like wants d/dz of this result
+            raise RuntimeError("gan_terms: the gradient cannot be differentiated a second time (create_graph=True); "
+                               "the op has a first derivative only")
+        saved = list(ctx.saved_tensors)
+        rc = saved.pop(0) if ctx.sides[0] else None
+        fc = saved.pop(0) if ctx.sides[1] else None
+        code, smooth = ctx.call
+        ups = [None if g is None else g.contiguous() for g in (g_g_real, g_g_fake, g_d_real, g_d_fake)]
+        # a side takes part when it is present, wanted, and one of its two terms is differentiated
+        if rc is None or not ctx.needs_input_grad[0] or (ups[0] is None and ups[2] is None):
+            rc, ups[0], ups[2] = None, None, None
+        if fc is None or not ctx.needs_input_grad[1] or (ups[1] is None and ups[3] is None):
+            fc, ups[1], ups[3] = None, None, None
+        if rc is None and fc is None:
+            return None, None, None, None
+        g_real = None if rc is None else torch.empty_like(rc)
+        g_fake = None if fc is None else torch.empty_like(fc)
+        table = (ctypes.c_void_p * 4)(*[None if g is None else g.data_ptr() for g in ups])
+        _call("vcg_gan_terms_bwd", _ptr(rc), 0 if rc is None else rc.numel(), _ptr(fc), 0 if fc is None else fc.numel(),
+              code, smooth, table, _ptr(g_real), _ptr(g_fake), _stream())
+        return g_real, g_fake, None, None
+
+
+def gan_terms(real, fake, objective, smooth=0.0):
+    """-> (g_real, g_fake, d_real, d_fake, mean_real, mean_fake), 0-dim fp32 tensors: the generator's and the discriminator's
+    adversarial terms on a discriminator's logits of real and of generated images, and the logit means.  `objective` is one of
+    GAN_OBJECTIVES; with s = `smooth` (one-sided label smoothing, 0 <= s < 0.5, 0 with the hinge) and
+    sp(t) = max(t, 0) + log1p(exp(-|t|)), each term is the mean over its tensor of
+
+        objective   d_real                      d_fake          g_real   g_fake
+        lsgan       (z - (1 - s))^2             z^2             z^2      (z - 1)^2
+        hinge       max(0, 1 - z)               max(0, 1 + z)   z        -z
+        logistic    (1 - s) sp(-z) + s sp(z)    sp(z)           sp(z)    sp(-z)
+
+    evaluated and summed in double and rounded once.  `real` or `fake` may be None (not both): its three results are 0 and carry no
+    gradient.  The four terms are differentiable once in the logits; the means carry no gradient."""
+    if objective not in GAN_OBJECTIVES:
+        raise RuntimeError(f"gan_terms: objective must be one of {GAN_OBJECTIVES}, got {objective!r}")
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, float)) or not math.isfinite(smooth) or not 0.0 <= smooth < 0.5:
+        raise RuntimeError(f"gan_terms: smooth must be a finite number in [0, 0.5), got {smooth!r}")
+    if objective == "hinge" and smooth != 0.0:
+        raise RuntimeError(f"gan_terms: the hinge objective takes no label smoothing, got smooth={smooth!r}")
+    if real is None and fake is None:
+        raise RuntimeError("gan_terms: real and fake are both None")
+    return _GanTermsFn.apply(real, fake, GAN_OBJECTIVES.index(objective), float(smooth))
+
+
 class _KLFn(torch.autograd.Function):
     """KLDivergenceLoss.forward; Losses.py:115-121."""
 

@@ -289,6 +289,49 @@ def check_image_size(architecture, image_size):
         raise ValueError(f"--image_size {image_size} is not usable with {architecture}: {e}") from None
 
 
+def gan_label_smooth_value(text):
+    """argparse type of --gan_label_smooth: a finite amount in [0, 0.5) (0: off)."""
+    try:
+        value = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not math.isfinite(value) or not 0.0 <= value < 0.5:
+        raise argparse.ArgumentTypeError(f"--gan_label_smooth must be finite and lie in [0, 0.5) (0: no smoothing), got {text}")
+    return value
+
+
+def gan_objective_of(args):
+    """configure_loss's adversarial-objective keywords from `args` (also one built without the parser), checked as the parser
+    checks them: refused for an architecture without a discriminator, and the smoothing refused with the hinge."""
+    objective = getattr(args, "gan_objective", "lsgan")
+    smooth = getattr(args, "gan_label_smooth", 0.0)
+    if objective not in ops.GAN_OBJECTIVES:
+        raise ValueError(f"--gan_objective must be one of {', '.join(ops.GAN_OBJECTIVES)}, got {objective!r}")
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, float)) or not math.isfinite(smooth) or not 0.0 <= smooth < 0.5:
+        raise ValueError(f"--gan_label_smooth must be finite and lie in [0, 0.5) (0: no smoothing), got {smooth!r}")
+    architecture = ALIASES.get(args.architecture, args.architecture)
+    for flag, given in (("--gan_objective", objective != "lsgan"), ("--gan_label_smooth", smooth != 0.0)):
+        if given and architecture not in POOL_ARCHS:
+            raise ValueError(f"{flag} is supported by {', '.join(POOL_ARCHS)} only: {architecture} has no discriminator, "
+                             "the flag would be ignored")
+    if objective == "hinge" and smooth != 0.0:
+        raise ValueError(f"--gan_label_smooth {smooth} cannot go with --gan_objective hinge: the hinge has no target to smooth "
+                         "(lsgan and logistic have)")
+    return {"gan_objective": objective, "gan_label_smooth": float(smooth)}
+
+
+class _Parser(argparse.ArgumentParser):
+    """The checks that look at two flags at once run when the command line is parsed, before anything touches the device."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        parsed, rest = super().parse_known_args(args, namespace)
+        try:
+            gan_objective_of(parsed)
+        except ValueError as e:
+            self.error(str(e))
+        return parsed, rest
+
+
 def pool_size_value(text):
     """argparse type of --pool_size: an integer >= 0 (0: off)."""
     try:
@@ -301,7 +344,7 @@ def pool_size_value(text):
 
 
 def build_parser():
-    p = argparse.ArgumentParser(description="Train VAE-CycleGAN models (MI355X-native path)")
+    p = _Parser(description="Train VAE-CycleGAN models (MI355X-native path)")
     p.add_argument("--architecture", type=str, default="autoencoder", choices=REFERENCE_ARCHS + list(ALIASES))
     p.add_argument("--paired", action="store_true", default=False)
     p.add_argument("--unpaired", dest="paired", action="store_false")
@@ -366,6 +409,13 @@ def build_parser():
                    help="image history pool of this many generated images per discriminator (" + ", ".join(POOL_ARCHS) + "): each "
                         "fake is shown to its discriminator as itself or, half of the time once the pool is full, exchanged "
                         "against a random stored one; 50 is the customary value; 0: off")
+    p.add_argument("--gan_objective", type=str, default="lsgan", choices=ops.GAN_OBJECTIVES,
+                   help="adversarial objective of the models with a discriminator (" + ", ".join(POOL_ARCHS) + "): lsgan, the "
+                        "reference's least squares; hinge; logistic, the non-saturating cross-entropy — the two to reach for "
+                        "where the least-squares terms saturate, as they do on the patch logits above 256 px")
+    p.add_argument("--gan_label_smooth", type=gan_label_smooth_value, default=0.0,
+                   help="one-sided label smoothing: the discriminator's real target becomes 1 - S (lsgan, logistic; not hinge); "
+                        "0: off")
     p.add_argument("--output_dir", type=str, default="runs")
     p.add_argument("--save_freq", type=int, default=10)
     p.add_argument("--log_image_freq", type=int, default=5)
@@ -478,6 +528,7 @@ def main(args):
     if image_kw["swd_levels"] not in (1, 2, 3):
         raise ValueError(f"--swd_levels must be 1, 2 or 3, got {image_kw['swd_levels']}")
     kl_kw = kl_control_of(args)
+    gan_kw = gan_objective_of(args)
     clip = getattr(args, "clip_grad_norm", 0.0)
     if not math.isfinite(clip) or clip < 0.0:
         raise ValueError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {clip}")
@@ -542,11 +593,13 @@ def main(args):
             print(f"Image history pool: {pool_size} images per discriminator")
     else:
         model.configure_optimizers(lr=args.lr, clip_grad_norm=clip, ema_decay=ema_decay)
+    if rank == 0 and (gan_kw["gan_objective"], gan_kw["gan_label_smooth"]) != ("lsgan", 0.0):
+        print(f"Adversarial objective: {gan_kw['gan_objective']}, label smoothing {gan_kw['gan_label_smooth']}")
     if ema_decay > 0.0 and rank == 0:
         print(f"Averaged generator weights (decay {ema_decay}): the test loss, and with it best_model.pth, is the averaged weights'")
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
                          lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
-                         swd_seed=ops.rank_seed(args.seed, rank) % 2 ** 32, **image_kw, **kl_kw)      # plans per rank, as the eps streams
+                         swd_seed=ops.rank_seed(args.seed, rank) % 2 ** 32, **image_kw, **kl_kw, **gan_kw)      # plans per rank, as the eps streams
     if world > 1:
         parallel.attach(model)
     same_xy = args.architecture in ("autoencoder", "vae")
