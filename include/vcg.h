@@ -261,6 +261,30 @@ int vcg_gan_terms_fwd(const float* real, size_t n_real, const float* fake, size_
    buffer is written whole (zeros where both its entries are null); an absent side's may be null. */
 int vcg_gan_terms_bwd(const float* real, size_t n_real, const float* fake, size_t n_fake, int objective, double smooth,
                       const float* const* g_out, float* g_real, float* g_fake, void* stream);
+/* Discriminator feature-matching loss (new: the reference has no such term).  n_layers in 1..VCG_FM_MAX_LAYERS layers; layer l is
+   fake[l], real[l]: rows[l] x cp fp32, the networks' NHWC buffers with rows = N h w, channels[l] logical channels at pitch
+   cp = 4 ceil(channels / 4) (the channel the fastest index), 16-byte aligned, pad lanes zero in both.  With L = n_layers and
+   k_l = 1 / (L rows_l channels_l):
+     VCG_FM_PAIR   out[0] = sum_l k_l sum_e |fake_l[e] - real_l[e]|                 the mean over the layers of their L1 means
+     VCG_FM_MEAN   out[0] = sum_l k_l rows_l sum_c |D_lc|,  D_lc = (1 / rows_l) sum_rows (fake_l - real_l)[row, c]
+                   signs[0 .. sum_l cp_l) = sign(D_lc), layer after layer at the layer's pitch (0 in the pad lanes), 16-byte aligned,
+                   kept by the caller for vcg_feature_match_bwd (null is accepted in the pair mode, which stores none)
+   Summands and sums in double, combined in a fixed order by further launches, no atomics, one rounding to fp32 at the store: the
+   same input gives the same bits.  A NaN anywhere in a layer gives a NaN result.  ws: vcg_feature_match_workspace(...) bytes (0
+   and vcg_last_error for bad arguments), 16-byte aligned.  vcg_feature_match_chunk(mode, channels): the work one workgroup takes
+   at a time — float4s of a layer per chunk (pair), rows per slab of a layer with that many channels (mean); what the tests place
+   their sizes around.  Refused (nothing launched): n_layers outside 1..4, an empty layer, a null pointer.  csrc/feature_match.hip. */
+enum { VCG_FM_PAIR = 0, VCG_FM_MEAN = 1, VCG_FM_MAX_LAYERS = 4 };
+size_t vcg_feature_match_chunk(int mode, int channels);
+size_t vcg_feature_match_workspace(const size_t* rows, const int* channels, int n_layers, int mode);
+int vcg_feature_match_fwd(const float* const* fake, const float* const* real, const size_t* rows, const int* channels,
+                          int n_layers, int mode, float* out, float* signs, void* ws, size_t ws_bytes, void* stream);
+/* The real side is a constant of the term.  One launch over all layers: with c_l = (float)((double)g_out[0] k_l), g_fake[l] =
+   c_l sign(fake_l - real_l) element by element (pair; fake and real are read again) or c_l sign(D_lc) broadcast over the rows
+   (mean; `signs` of the forward, fake and real may be null), sign(0) = 0, pad lanes 0, written whole.  A null g_fake[l]: that layer
+   needs no gradient and is skipped; all null: nothing is launched.  g_out is read on the device. */
+int vcg_feature_match_bwd(const float* const* fake, const float* const* real, const float* signs, const float* g_out,
+                          float* const* g_fake, const size_t* rows, const int* channels, int n_layers, int mode, void* stream);
 /* KLDivergenceLoss — Losses.py:115-121                                       */
 int vcg_kl_fwd(const float* mu, const float* lv, float* out, size_t n,
                void* ws, size_t ws_bytes, void* stream);

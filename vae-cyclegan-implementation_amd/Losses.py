@@ -220,6 +220,22 @@ class GANLossDiscriminator(nn.Module):
         return ops.weighted_sum([real_loss, fake_loss], [1.0, 1.0]), real_loss, fake_loss
 
 
+class FeatureMatchingLoss(nn.Module):
+    """Discriminator feature matching (ops.feature_matching; new: the reference has no such term): the mean over a discriminator's
+    blocks of the distance between its activations on the generated and on the real batch, the real side a constant.  `mode`, one
+    of ops.FM_MODES: "pair", the element-wise L1 of pix2pixHD (Wang et al. 2018) for batches whose images correspond; "mean", the
+    L1 between the per-channel expected features (Salimans et al. 2016), which needs no pairing."""
+
+    def __init__(self, mode="mean"):
+        super().__init__()
+        if not isinstance(mode, str) or mode not in ops.FM_MODES:
+            raise ValueError(f"mode must be one of {', '.join(ops.FM_MODES)}, got {mode!r}")
+        self.mode = mode
+
+    def forward(self, fake_features, real_features):
+        return ops.feature_matching(list(fake_features), list(real_features), self.mode)
+
+
 class KLDivergenceLoss(nn.Module):
     """-0.5 * mean(1 + clamp(logvar) - mu^2 - exp(clamp(logvar)))  (reference Losses.py:105-121).
 

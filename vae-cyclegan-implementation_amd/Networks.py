@@ -20,8 +20,8 @@ import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
 from . import ops
-from .Losses import (IMAGE_TERMS, LSGAN, CycleConsistencyLoss, GANLossDiscriminator, GANLossGenerator, IdentityLoss,
-                     KLDivergenceLoss, MultiScaleStructuralLoss, SlicedWassersteinLoss, TranslationLoss, gan_objective)
+from .Losses import (IMAGE_TERMS, LSGAN, CycleConsistencyLoss, FeatureMatchingLoss, GANLossDiscriminator, GANLossGenerator,
+                     IdentityLoss, KLDivergenceLoss, MultiScaleStructuralLoss, SlicedWassersteinLoss, TranslationLoss, gan_objective)
 from .image_pool import ImagePool, pool_seed as _pool_seed
 from .optim import FusedAdam, kl_weight_at
 
@@ -282,6 +282,19 @@ class Discriminator(nn.Module):
             x = blk(x)
         head = layers[-1]
         return ops.fullmap_sn_conv(x, head.weight_orig, head.bias, head.weight_u, head.weight_v, self.training)
+
+    def features(self, x):
+        """-> ([a1, a2, a3, a4], logits) from one pass: the outputs of the four CaSb blocks (after InstanceNorm and LeakyReLU) that
+        `forward` hands from block to block, and its logits — the same launches, the same bits.  What the feature-matching term
+        compares (_GanMixin._add_fm)."""
+        x = ops.to_nhwc(x)
+        layers = list(self.model)
+        acts = []
+        for blk in layers[:-1]:
+            x = blk(x)
+            acts.append(x)
+        head = layers[-1]
+        return acts, ops.fullmap_sn_conv(x, head.weight_orig, head.bias, head.weight_u, head.weight_v, self.training)
 
 
 # --------------------------------------------------------------------------- composites
@@ -617,6 +630,25 @@ def _configure_gan(model, kwargs):
     return GANLossGenerator(*model.gan_objective), GANLossDiscriminator(*model.gan_objective)
 
 
+def _fm_config(kwargs):
+    """The validated (lambda_fm, fm_mode) of a configure_loss call."""
+    lam, mode = kwargs.get("lambda_fm", 0.0), kwargs.get("fm_mode", "mean")
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not math.isfinite(lam) or lam < 0.0:
+        raise ValueError(f"lambda_fm must be finite and >= 0, got {lam!r}")
+    if not isinstance(mode, str) or mode not in ops.FM_MODES:
+        raise ValueError(f"fm_mode must be one of {', '.join(ops.FM_MODES)}, got {mode!r}")
+    return float(lam), mode
+
+
+def _refuse_fm(model, kwargs):
+    """configure_loss of the models without a discriminator takes the keywords so that one call fits every architecture: a weight
+    of 0 is ignored."""
+    lam, _ = _fm_config(kwargs)
+    if lam != 0.0:
+        raise ValueError(f"lambda_fm={lam}: {type(model).__name__} has no discriminator whose features could be matched "
+                         f"({GAN_MODELS} have)")
+
+
 class _GanTerms:
     """The adversarial terms of one discriminator's logits on real and on generated images (either may be None) under a model's
     objective, each a (term, logit mean) pair.  LSGAN without smoothing: every term is its own ops.mse_const call, issued where
@@ -761,6 +793,42 @@ class _GanMixin(_PoolMixin, _OptimizerStatesMixin):
     optimizer_G): the optimizer pair and the alternating G then D update."""
     _opt_names = ("optimizer_G", "optimizer_D")
     gan_objective = LSGAN                        # configure_loss(gan_objective=..., gan_label_smooth=...) replaces it
+    fm_term = None                               # (weight, FeatureMatchingLoss) after configure_loss(lambda_fm > 0, fm_mode=...)
+
+    def _configure_fm(self, kwargs):
+        """The discriminator feature-matching term of a GAN model: lambda_fm times, per discriminator, the distance between its
+        block activations on the generated batch and on the real one (Losses.FeatureMatchingLoss), the real side a constant.  It
+        sits in G_loss alone: the G-phase backward takes the discriminators' data gradient only (`_alternating_step`), the D phase
+        differentiates D_loss, so the discriminator update is the one without the term.  With the weight at its default 0
+        `fm_term` is None: no loss object exists, and the step computes, launches and reports exactly what it did before.  The
+        element-wise mode needs batches whose images correspond, which an unpaired cycle model's do not."""
+        lam, mode = _fm_config(kwargs)
+        if mode == "pair" and not getattr(self, "paired", True):
+            raise ValueError(f"fm_mode='pair': the batches of an unpaired {type(self).__name__} are not aligned image by image; "
+                             "use fm_mode='mean', which matches the expected features")
+        self.fm_term = None if lam == 0.0 else (lam, FeatureMatchingLoss(mode))
+
+    @property
+    def fm_enabled(self):
+        return self.fm_term is not None
+
+    def _disc(self, D, image):
+        """One discriminator pass -> (block activations or None, logits): the activations only when the term wants them."""
+        return D.features(image) if self.fm_term is not None else (None, D(image))
+
+    def _add_fm(self, t, terms, weights, pairs):
+        """Appends the term on the (generated, real) activation lists of the step's discriminators to the generator objective's
+        (terms, weights) and to the step's scalars `t`; on the main stream, after the direction join."""
+        if self.fm_term is not None:
+            lam, fn = self.fm_term
+            values = [fn(fake, real) for fake, real in pairs]
+            t["loss_fm"] = values[0] if len(values) == 1 else ops.weighted_sum(values, [1.0] * len(values))
+            terms.append(t["loss_fm"])
+            weights.append(lam)
+
+    def _fm_spec(self, spec):
+        """`spec` (_report) with loss_fm after the keys the model reports without the term; unchanged with the weight 0."""
+        return spec + (_same("loss_fm") if self.fm_term is not None else ())
 
     def _gan_optimizers(self, lr, betas, clip_grad_norm, ema_decay, pool_size, pool_seed):
         # pool_size > 0: an image history pool of that many images per discriminator (DX pools F(y), DY pools G(x), D pools G(x)),
@@ -858,6 +926,7 @@ class Autoencoder(_OptimizerStatesMixin, nn.Module):
         _refuse_swd(self, kwargs)
         _refuse_kl_control(self, kwargs)
         _refuse_gan_objective(self, kwargs)
+        _refuse_fm(self, kwargs)
         self.loss_fn = TranslationLoss()
         self.image_terms = _image_terms(kwargs)
 
@@ -963,6 +1032,7 @@ class VariationalAutoencoder(_OptimizerStatesMixin, nn.Module):
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
         _refuse_gan_objective(self, kwargs)
+        _refuse_fm(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
         self.loss_kl_fn = _configure_kl(self, kwargs)
         self.image_terms = _image_terms(kwargs)
@@ -1082,17 +1152,20 @@ def _two_directions(G, F, x, y, fork=None, tickets=None, identity=None):
     return rs, (), Gy, Fx
 
 
-def _discriminate(DY, DX, Gx, Fy, x, y, fork=None):
+def _discriminate(DY, DX, Gx, Fy, x, y, fork=None, run=None):
     """-> DY(G(x)), DX(F(y)), DX(x), DY(y), issued DY(G(x)), DX(F(y)), DY(y), DX(x): alternately on the two streams of `fork`
     (32.64 -> 32.42 ms over three A/B pairs), each discriminator seeing its fake before its real batch as in the reference
-    (spectral norm's power iteration advances per call)."""
+    (spectral norm's power iteration advances per call).  `run(D, image)`, if given, stands for D(image) (_GanMixin._disc: each
+    result is then an (activations, logits) pair)."""
     second = fork.second if fork is not None else contextlib.nullcontext
-    DYGx = DY(Gx)
+    if run is None:
+        run = lambda D, image: D(image)          # noqa: E731
+    DYGx = run(DY, Gx)
     with second():
-        DXFy = DX(Fy)
-    DYy = DY(y)
+        DXFy = run(DX, Fy)
+    DYy = run(DY, y)
     with second():
-        DXx = DX(x)
+        DXx = run(DX, x)
     return DYGx, DXFy, DXx, DYy
 
 
@@ -1174,6 +1247,7 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
         self.lambda_cycle = kwargs.get("lambda_cycle", 10.0)
         self.image_terms = _image_terms(kwargs)
         self._configure_swd(kwargs)
+        self._configure_fm(kwargs)
 
     def _check_configured(self, need_opt=True):
         if (self.loss_cycle is None or self.loss_gan_gen is None or self.loss_gan_disc is None
@@ -1209,7 +1283,7 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
             fork = _fork(x, y)
         (Gx, FGx, Fy, GFy), stats, Gy, Fx = _two_directions(self.G, self.F, x, y, fork, tickets,
                                                              self._identity_pass if self._variational else None)
-        DYGx, DXFy, DXx, DYy = _discriminate(self.DY, self.DX, Gx, Fy, x, y, fork)
+        (aDYGx, DYGx), (aDXFy, DXFy), (aDXx, DXx), (aDYy, DYy) = _discriminate(self.DY, self.DX, Gx, Fy, x, y, fork, self._disc)
         if fork is not None:
             fork.join()
 
@@ -1238,6 +1312,8 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
         t.update(extra)
         terms, weights = terms + list(extra.values()), weights + extra_weights
         self._add_swd(t, terms, weights, Gx, Fy, x, y)     # the translated batches against the other domain's: needs no pairing
+        # fm(DY: G(x) against y) + fm(DX: F(y) against x), on the shared discriminator passes; both streams are joined by now
+        self._add_fm(t, terms, weights, [(aDYGx, aDYy), (aDXFy, aDXx)])
         t["G_loss"] = ops.weighted_sum(terms, weights)
         # discriminator objective on the SAME discriminator outputs (reference :2038-2040)
         t["D_loss_x_real"], _ = gan_x.d_real()
@@ -1258,8 +1334,8 @@ class CycleVAEGAN(_SwdMixin, _GanMixin, nn.Module):
         if self.paired:
             keys += ("loss_identity",)
         keys += tuple(name for name, _, _ in self.image_terms)
-        return _kl_keys(self, (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + self._swd_spec() + (() if training else _GX_FY),
-                        training)
+        return self._fm_spec(_kl_keys(self, (("total_loss", ("G_loss", "D_loss")),) + _same(*keys) + self._swd_spec()
+                                      + (() if training else _GX_FY), training))
 
     def _pooled_d_terms(self, t, Gx, Fy):
         """The discriminators' fake terms with image history pools (_PoolMixin), after the forward (both direction streams are
@@ -1418,6 +1494,7 @@ class CycleAE(_CycleNoGAN):
 
     def configure_loss(self, **kwargs):
         _refuse_gan_objective(self, kwargs)
+        _refuse_fm(self, kwargs)
         self.loss_cycle = CycleConsistencyLoss()
         if self.paired:
             self.loss_trans = TranslationLoss()
@@ -1439,6 +1516,7 @@ class CycleVAE(_CycleNoGAN):
 
     def configure_loss(self, **kwargs):
         _refuse_gan_objective(self, kwargs)
+        _refuse_fm(self, kwargs)
         self.loss_cycle = CycleConsistencyLoss()
         if self.paired:
             self.loss_trans = TranslationLoss()
@@ -1518,6 +1596,7 @@ class DoubleAutoencoder(_DoubleStep):
         _refuse_swd(self, kwargs)
         _refuse_kl_control(self, kwargs)
         _refuse_gan_objective(self, kwargs)
+        _refuse_fm(self, kwargs)
         self.loss_fn = TranslationLoss()
 
     def _check_configured(self, need_opt=True):
@@ -1622,6 +1701,7 @@ class DoubleVariationalAutoencoder(_DoubleStep):
     def configure_loss(self, **kwargs):
         _refuse_swd(self, kwargs)
         _refuse_gan_objective(self, kwargs)
+        _refuse_fm(self, kwargs)
         self.loss_trans_fn = TranslationLoss()
         self.loss_kl_fn = _configure_kl(self, kwargs)
 
@@ -1683,12 +1763,12 @@ class _SingleGAN(_GanMixin, nn.Module):
         if self.image_pools:
             self._pooled_d_terms(t, Gx)
         self._alternating_step(t["G_loss"], t.get("D_loss_backward", t["D_loss"]))
-        return _report(self, t, _kl_keys(self, self._TRAIN, True), True, **_kl_host(self, True))
+        return _report(self, t, self._fm_spec(_kl_keys(self, self._TRAIN, True)), True, **_kl_host(self, True))
 
     def validation_step(self, batch):
         with torch.no_grad():
             t, Gx = self._losses(batch)
-            return _report(self, t, _kl_keys(self, self._VALIDATION, False), False, Gx=Gx)
+            return _report(self, t, self._fm_spec(_kl_keys(self, self._VALIDATION, False)), False, Gx=Gx)
 
 
 class AEGAN(_SingleGAN):
@@ -1732,6 +1812,7 @@ class AEGAN(_SingleGAN):
         self.loss_identity_fn = TranslationLoss()
         self.lambda_gan = kwargs.get("lambda_gan", 1.0)
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
+        self._configure_fm(kwargs)
 
     def _check_configured(self):
         if self.optimizer_G is None or self.optimizer_D is None:
@@ -1747,10 +1828,17 @@ class AEGAN(_SingleGAN):
 
     def _losses(self, batch, training=False):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
-        Gx, Gy, DGx, Dy = self(x, y)
+        if self.fm_term is None:
+            Gx, Gy, DGx, Dy = self(x, y)
+            aDGx = aDy = None
+        else:                                    # `forward` with the discriminator's block activations kept
+            Gx, Gy = self.G(x), self.G(y)
+            (aDGx, DGx), (aDy, Dy) = self._disc(self.D, Gx), self._disc(self.D, y)
         t = {"loss_trans": self.loss_trans_fn(Gx, y), "loss_identity": self.loss_identity_fn(Gy, y)}
         self._gan_terms(t, DGx, Dy)
-        t["G_loss"] = ops.weighted_sum([t["loss_trans"], t["gan_g"], t["loss_identity"]], [1.0, self.lambda_gan, self.lambda_identity])
+        terms, weights = [t["loss_trans"], t["gan_g"], t["loss_identity"]], [1.0, self.lambda_gan, self.lambda_identity]
+        self._add_fm(t, terms, weights, [(aDGx, aDy)])
+        t["G_loss"] = ops.weighted_sum(terms, weights)
         return t, Gx
 
     def validation_step(self, batch):
@@ -1793,6 +1881,7 @@ class VAEGAN(_SingleGAN):
         self.lambda_gan = kwargs.get("lambda_gan", 1.0)
         self.lambda_identity = kwargs.get("lambda_identity", 5.0)
         self.lambda_recon = kwargs.get("lambda_recon", 1.0)
+        self._configure_fm(kwargs)
 
     def enable_debug_mode(self, enabled=True):
         self.debug_mode = enabled
@@ -1803,13 +1892,20 @@ class VAEGAN(_SingleGAN):
 
     def _losses(self, batch, training=False):
         x, y = ops.to_nhwc(batch["x"]), ops.to_nhwc(batch["y"])
-        Gx, mu, logvar, Gy, _, _, DGx, Dy = self(x, y)
+        if self.fm_term is None:
+            Gx, mu, logvar, Gy, _, _, DGx, Dy = self(x, y)
+            aDGx = aDy = None
+        else:                                    # `forward` with the discriminator's block activations kept
+            (Gx, mu, logvar), (Gy, _, _) = self.G(x), self.G(y)
+            (aDGx, DGx), (aDy, Dy) = self._disc(self.D, Gx), self._disc(self.D, y)
         t = {"loss_trans": self.translation_loss(Gx, y), "loss_identity": self.identity_loss(Gy, y)}
         kl, kl_objective, _ = _kl_terms(self.kl_loss, [(mu, logvar)])
         t.update(kl)
         self._gan_terms(t, DGx, Dy)
-        t["G_loss"] = ops.weighted_sum([t["loss_trans"], t["gan_g"], t["loss_identity"], kl_objective],
-                                       [self.lambda_recon, self.lambda_gan, self.lambda_identity, _kl_weight(self, training)])
+        terms = [t["loss_trans"], t["gan_g"], t["loss_identity"], kl_objective]
+        weights = [self.lambda_recon, self.lambda_gan, self.lambda_identity, _kl_weight(self, training)]
+        self._add_fm(t, terms, weights, [(aDGx, aDy)])
+        t["G_loss"] = ops.weighted_sum(terms, weights)
         # the reference detaches the discriminator OUTPUT of the fake branch (`gan_loss_disc(Dy, DGx.detach())`, :1277),
         # not its input: the fake term is a constant in D_loss and only (1 - D(y))^2 reaches D's parameters.  Kept as
         # written — D_loss reports both terms, the backward pass sees the real one.

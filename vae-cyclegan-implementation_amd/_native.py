@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # VCG_LIBVCG: load another build of the same sources (A/B runs of kernel variants, tools/); the default is the in-tree library
 LIB_PATH = os.environ.get("VCG_LIBVCG") or os.path.join(_HERE, "libvcg.so")
-SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip", "swd_loss.hip", "msssim_loss.hip", "kl_free_bits.hip", "patch_head.hip", "gan_terms.hip"]
+SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip", "swd_loss.hip", "msssim_loss.hip", "kl_free_bits.hip", "patch_head.hip", "gan_terms.hip", "feature_match.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vcg.h")
 
 _c = ctypes
@@ -23,6 +23,8 @@ _D = _c.c_double
 _U64 = _c.c_uint64
 _I32P = _c.POINTER(_c.c_int32)
 _U64P = _c.POINTER(_c.c_uint64)
+_ZP = _c.POINTER(_c.c_size_t)
+_IP = _c.POINTER(_c.c_int)
 
 # name -> (restype, argtypes); mirrors include/vcg.h one to one
 SIGNATURES = {
@@ -92,6 +94,10 @@ SIGNATURES = {
     "vcg_mse_const_bwd": (_I, [_P, _F, _P, _P, _Z, _P]),
     "vcg_gan_terms_fwd": (_I, [_P, _Z, _P, _Z, _I, _D, _P, _P]),
     "vcg_gan_terms_bwd": (_I, [_P, _Z, _P, _Z, _I, _D, _c.POINTER(_P), _P, _P, _P]),
+    "vcg_feature_match_chunk": (_Z, [_I, _I]),
+    "vcg_feature_match_workspace": (_Z, [_ZP, _IP, _I, _I]),
+    "vcg_feature_match_fwd": (_I, [_c.POINTER(_P), _c.POINTER(_P), _ZP, _IP, _I, _I, _P, _P, _P, _Z, _P]),
+    "vcg_feature_match_bwd": (_I, [_c.POINTER(_P), _c.POINTER(_P), _P, _P, _c.POINTER(_P), _ZP, _IP, _I, _I, _P]),
     "vcg_kl_fwd": (_I, [_P, _P, _P, _Z, _P, _Z, _P]),
     "vcg_kl_bwd": (_I, [_P, _P, _P, _P, _P, _Z, _P]),
     "vcg_kl_fb_workspace": (_Z, [_Z, _I]),

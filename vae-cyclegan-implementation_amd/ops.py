@@ -1497,6 +1497,104 @@ def gan_terms(real, fake, objective, smooth=0.0):
     return _GanTermsFn.apply(real, fake, GAN_OBJECTIVES.index(objective), float(smooth))
 
 
+FM_MODES = ("pair", "mean")                          # the index is the library's VCG_FM_* code
+FM_MAX_LAYERS = 4                                    # VCG_FM_MAX_LAYERS
+
+
+def fm_chunk(mode, channels=4):
+    """The work one workgroup of the feature-matching kernels takes at a time (vcg_feature_match_chunk): float4s of a layer per
+    chunk in the pair mode — rows, for a layer of 1..4 channels —, rows per slab of a layer with `channels` channels in the mean
+    mode.  The sizes at which the kernels change path; the tests place their shapes around them."""
+    if mode not in FM_MODES:
+        raise RuntimeError(f"fm_chunk: mode must be one of {FM_MODES}, got {mode!r}")
+    return _scratch("vcg_feature_match_chunk", FM_MODES.index(mode), int(channels))
+
+
+class _FeatureMatchFn(torch.autograd.Function):
+    """The feature-matching term of up to four (generated, real) activation pairs (csrc/feature_match.hip): two launches forward
+    (three in the mean mode), one backward, each for all layers.  The real side is a constant: its inputs get None, so autograd does not walk the real pass."""
+
+    @staticmethod
+    def forward(ctx, code, n, *tensors):
+        fakes, reals = tensors[:n], tensors[n:]
+        fp, rp = [as_phys(t) for t in fakes], [as_phys(t) for t in reals]
+        dev = fakes[0].device
+        rows = (ctypes.c_size_t * n)(*[p.shape[0] * p.shape[1] * p.shape[2] for p in fp])
+        chans = (ctypes.c_int * n)(*[t.shape[1] for t in fakes])
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        signs = torch.empty(sum(pitch(t.shape[1]) for t in fakes), dtype=torch.float32, device=dev) if code == 1 else None
+        ws = workspace(_scratch("vcg_feature_match_workspace", rows, chans, n, code), dev)
+        _call("vcg_feature_match_fwd", (ctypes.c_void_p * n)(*[p.data_ptr() for p in fp]),
+              (ctypes.c_void_p * n)(*[p.data_ptr() for p in rp]), rows, chans, n, code, _ptr(out), _ptr(signs), _ptr(ws),
+              ws.numel() * 4, _stream())
+        # pair: the sign is recomputed from the operands; mean: the channel signs stand for both
+        ctx.save_for_backward(*(fp + rp if code == 0 else [signs]))
+        ctx.call = (code, n, [tuple(t.shape) for t in fakes])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():               # create_graph=True
+            raise RuntimeError("feature_matching: the gradient cannot be differentiated a second time (create_graph=True); "
+                               "the op has a first derivative only")
+        code, n, shapes = ctx.call
+        wanted = [ctx.needs_input_grad[2 + i] for i in range(n)]
+        if not any(wanted):
+            return (None,) * (2 + 2 * n)
+        saved = ctx.saved_tensors
+        fp, rp, signs = (saved[:n], saved[n:], None) if code == 0 else (None, None, saved[0])
+        g = g.contiguous()
+        dev = g.device
+        grads = [torch.empty((s[0], s[2], s[3], pitch(s[1])), dtype=torch.float32, device=dev) if w else None
+                 for s, w in zip(shapes, wanted)]
+
+        def table(ts):
+            return (ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in ts])
+        rows = (ctypes.c_size_t * n)(*[s[0] * s[2] * s[3] for s in shapes])
+        chans = (ctypes.c_int * n)(*[s[1] for s in shapes])
+        _call("vcg_feature_match_bwd", None if fp is None else table(fp), None if rp is None else table(rp), _ptr(signs), _ptr(g),
+              table(grads), rows, chans, n, code, _stream())
+        return (None, None, *[None if t is None else logical_of(t, s[1]) for t, s in zip(grads, shapes)], *([None] * n))
+
+
+def feature_matching(fakes, reals, mode):
+    """The discriminator feature-matching term -> a 0-dim fp32 tensor.  `fakes`, `reals`: sequences of 1..4 logical (N, C, H, W)
+    activations with equal shapes pairwise — a discriminator's block outputs on the generated and on the real batch.  With L layers,
+    fm = (1 / L) sum_l term_l and `mode` one of FM_MODES:
+
+        pair   term_l = mean over all elements of |f_l - r_l|                       (pix2pixHD; image i of the fakes belongs to image i of
+                                                                                     the reals)
+        mean   term_l = (1 / C_l) sum_c |mean_{n,h,w} f_l[:, c] - mean_{n,h,w} r_l[:, c]|   (Salimans et al. 2016; needs no pairing)
+
+    summed in double and rounded once.  The reals are constants of the term: it is differentiable once in each fake, with
+    sign(0) = 0, and every real gets None."""
+    for name, seq in (("fakes", fakes), ("reals", reals)):
+        if not isinstance(seq, (list, tuple)):
+            raise RuntimeError(f"feature_matching: {name} must be a list or tuple of tensors, got {type(seq).__name__}")
+        if not 1 <= len(seq) <= FM_MAX_LAYERS:
+            raise RuntimeError(f"feature_matching: {name} must hold 1..{FM_MAX_LAYERS} layers, got {len(seq)}")
+        for i, t in enumerate(seq):
+            if not isinstance(t, torch.Tensor):
+                raise RuntimeError(f"feature_matching: {name}[{i}] is not a tensor but {type(t).__name__}")
+            if t.dim() != 4:
+                raise RuntimeError(f"feature_matching: {name}[{i}] must be an (N, C, H, W) tensor, got shape {tuple(t.shape)}")
+            if t.numel() == 0:
+                raise RuntimeError(f"feature_matching: {name}[{i}] is empty, shape {tuple(t.shape)}")
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"feature_matching: {name}[{i}]: expected float32, got {t.dtype}")
+    if len(fakes) != len(reals):
+        raise RuntimeError(f"feature_matching: fakes has {len(fakes)} layers, reals {len(reals)}")
+    for i, (f, r) in enumerate(zip(fakes, reals)):
+        if f.shape != r.shape:
+            raise RuntimeError(f"feature_matching: fakes[{i}] has shape {tuple(f.shape)}, reals[{i}] {tuple(r.shape)}")
+    if mode not in FM_MODES:
+        raise RuntimeError(f"feature_matching: mode must be one of {FM_MODES}, got {mode!r}")
+    for name, seq in (("fakes", fakes), ("reals", reals)):
+        for i, t in enumerate(seq):
+            _require_gpu(t, f"feature_matching: {name}[{i}]")
+    return _FeatureMatchFn.apply(FM_MODES.index(mode), len(fakes), *fakes, *reals)
+
+
 class _KLFn(torch.autograd.Function):
     """KLDivergenceLoss.forward; Losses.py:115-121."""
 

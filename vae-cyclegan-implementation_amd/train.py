@@ -320,6 +320,27 @@ def gan_objective_of(args):
     return {"gan_objective": objective, "gan_label_smooth": float(smooth)}
 
 
+def feature_matching_of(args):
+    """configure_loss's feature-matching keywords from `args` (also one built without the parser), checked as the parser checks
+    them: refused for an architecture without a discriminator, and the element-wise mode refused for an unpaired cycle model."""
+    weight = getattr(args, "lambda_fm", 0.0)
+    mode = getattr(args, "fm_mode", "mean")
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not math.isfinite(weight) or weight < 0.0:
+        raise ValueError(f"--lambda_fm must be finite and >= 0 (0: the term is not computed), got {weight!r}")
+    if mode not in ops.FM_MODES:
+        raise ValueError(f"--fm_mode must be one of {', '.join(ops.FM_MODES)}, got {mode!r}")
+    architecture = ALIASES.get(args.architecture, args.architecture)
+    for flag, given in (("--lambda_fm", weight != 0.0), ("--fm_mode", mode != "mean")):
+        if given and architecture not in POOL_ARCHS:
+            raise ValueError(f"{flag} is supported by {', '.join(POOL_ARCHS)} only: {architecture} has no discriminator, "
+                             "the flag would be ignored")
+    unpaired = not getattr(args, "paired", False) or getattr(args, "dataset", None) == "summer2winter"
+    if mode == "pair" and architecture in ("cycleaegan", "cyclevaegan") and unpaired:
+        raise ValueError(f"--fm_mode pair needs batches whose images correspond, which an unpaired {architecture} run does not "
+                         "have (--paired, or --fm_mode mean: match the expected features)")
+    return {"lambda_fm": float(weight), "fm_mode": mode}
+
+
 class _Parser(argparse.ArgumentParser):
     """The checks that look at two flags at once run when the command line is parsed, before anything touches the device."""
 
@@ -327,6 +348,7 @@ class _Parser(argparse.ArgumentParser):
         parsed, rest = super().parse_known_args(args, namespace)
         try:
             gan_objective_of(parsed)
+            feature_matching_of(parsed)
         except ValueError as e:
             self.error(str(e))
         return parsed, rest
@@ -416,6 +438,15 @@ def build_parser():
     p.add_argument("--gan_label_smooth", type=gan_label_smooth_value, default=0.0,
                    help="one-sided label smoothing: the discriminator's real target becomes 1 - S (lsgan, logistic; not hinge); "
                         "0: off")
+    p.add_argument("--lambda_fm", type=_nonneg("--lambda_fm", " (0: the term is not computed)"), default=0.0,
+                   help="weight of the discriminator feature-matching term in the generator objective (" + ", ".join(POOL_ARCHS)
+                        + "): the generator is also asked to reproduce the activations of the discriminator's four blocks on real "
+                        "images, which steadies training with --gan_objective hinge, small batches and the patch head; 10 is the "
+                        "customary value; the discriminator update is not touched; 0: not computed")
+    p.add_argument("--fm_mode", type=str, default="mean", choices=ops.FM_MODES,
+                   help="what the feature-matching term compares: mean, the per-channel expected features of the two batches "
+                        "(needs no pairing); pair, the activations element by element (pix2pixHD; aegan, vaegan and paired cycle "
+                        "models, whose batches correspond image by image)")
     p.add_argument("--output_dir", type=str, default="runs")
     p.add_argument("--save_freq", type=int, default=10)
     p.add_argument("--log_image_freq", type=int, default=5)
@@ -529,6 +560,7 @@ def main(args):
         raise ValueError(f"--swd_levels must be 1, 2 or 3, got {image_kw['swd_levels']}")
     kl_kw = kl_control_of(args)
     gan_kw = gan_objective_of(args)
+    fm_kw = feature_matching_of(args)
     clip = getattr(args, "clip_grad_norm", 0.0)
     if not math.isfinite(clip) or clip < 0.0:
         raise ValueError(f"--clip_grad_norm must be finite and >= 0 (0 switches clipping off), got {clip}")
@@ -595,11 +627,13 @@ def main(args):
         model.configure_optimizers(lr=args.lr, clip_grad_norm=clip, ema_decay=ema_decay)
     if rank == 0 and (gan_kw["gan_objective"], gan_kw["gan_label_smooth"]) != ("lsgan", 0.0):
         print(f"Adversarial objective: {gan_kw['gan_objective']}, label smoothing {gan_kw['gan_label_smooth']}")
+    if rank == 0 and fm_kw["lambda_fm"] > 0.0:
+        print(f"Discriminator feature matching: weight {fm_kw['lambda_fm']}, mode {fm_kw['fm_mode']}")
     if ema_decay > 0.0 and rank == 0:
         print(f"Averaged generator weights (decay {ema_decay}): the test loss, and with it best_model.pth, is the averaged weights'")
     model.configure_loss(lambda_kl=args.lambda_kl, lambda_gan=args.lambda_gan, lambda_identity=args.lambda_identity,
                          lambda_cycle=args.lambda_cycle, lambda_recon=args.lambda_recon,
-                         swd_seed=ops.rank_seed(args.seed, rank) % 2 ** 32, **image_kw, **kl_kw, **gan_kw)      # plans per rank, as the eps streams
+                         swd_seed=ops.rank_seed(args.seed, rank) % 2 ** 32, **image_kw, **kl_kw, **gan_kw, **fm_kw)      # plans per rank, as the eps streams
     if world > 1:
         parallel.attach(model)
     same_xy = args.architecture in ("autoencoder", "vae")
