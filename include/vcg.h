@@ -600,6 +600,52 @@ size_t vcg_spread_workspace(int N, int H, int W);
 int vcg_spread_display_hw(const float* m2, int count, float gain, float* out_f32, unsigned char* out_u8, float* result, int N,
                           int Hp, int Wp, int top, int left, int H, int W, void* ws, size_t ws_bytes, void* stream);
 
+/* The interpolating translator (translate.py --interpolate N; new: the reference has no inference path) — csrc/latent_path.hip.
+   Latent maps are in the networks' physical layout, (h, w, pitch) fp32 with C <= pitch logical channels per pixel: `per` =
+   h w pitch floats per map.  A pair p is (a[p], b[p]); a and b each point at P consecutive maps and are only read, so they may
+   overlap: a = mu, b = mu + per makes the consecutive frames of one encoder batch the pairs, without a copy.  Pad lanes
+   (channels C .. pitch - 1) never enter a sum or an output: a NaN there does no harm. */
+#define VCG_LATENT_SLERP 0
+#define VCG_LATENT_LERP 1
+/* Below this sin(omega) the slerp uses the lerp coefficients.  sin(omega) < 1e-4 means the pair is within 1e-4 rad of parallel or
+   antiparallel; for the parallel case sin((1 - t) omega) / sin(omega) = (1 - t) (1 + O(omega^2)), so the two coefficient sets
+   differ by about omega^2 = 1e-8 relative, under the 6e-8 of fp32 rounding — the switch cannot be seen in z — while the division
+   by sin(omega) stays far from 0 / 0.  Antiparallel maps have no unique great circle; the straight line is the fallback there too. */
+#define VCG_SLERP_MIN_SIN 1e-4
+/* out[p] = [sum a[p]^2, sum b[p]^2, sum a[p] b[p]] over the logical channels, (P, 3) doubles; every summand (exact: a product of
+   two fp32 values) and every sum in double, because omega = acos(sum ab / sqrt(sum a^2 sum b^2)) loses half the digits of its
+   argument near parallel pairs.  Wave shuffles, then LDS in wavefront order; each workgroup writes one partial to a slot of its
+   own in ws and a final launch sums a pair's slots in a fixed order (csrc/metrics.hip's scheme): no atomics, the same bits on
+   every call, and a pair's numbers do not depend on P or on the other pairs (the slot count is a function of per alone).
+   ws: vcg_latent_stats_workspace(P, per) bytes (host arithmetic; 0 and vcg_last_error for P < 1, per == 0, per % 4 != 0 or
+   per > 2^31).
+   Refused (non-zero, vcg_last_error, nothing launched): a null pointer; P < 1; per == 0 or > 2^31; pitch % 4 != 0, C < 1,
+   C > pitch or per % pitch != 0; a or b not 16-byte aligned, out or ws not 8-byte aligned; a workspace that is too small. */
+size_t vcg_latent_stats_workspace(int P, size_t per);
+int vcg_latent_pair_stats(const float* a, const float* b, double* out, int P, size_t per, int C, int pitch, void* ws,
+                          size_t ws_bytes, void* stream);
+/* The fractions j = first .. first + k - 1 of the T >= 2 uniform fractions t_j = j / (T - 1) of every pair's path:
+     z[(p, j)] = ca a[p] + cb b[p],  z (P, k, per), fraction-major within a pair (the decoder-batch order of vcg_reparam_many_fwd).
+   (ca, cb) of a (pair, j) are evaluated in double and rounded once to fp32:
+     VCG_LATENT_LERP    (1 - t, t);
+     VCG_LATENT_SLERP   omega = acos(clamp(sum ab / sqrt(sum a^2 sum b^2), -1, 1)) from `stats` (vcg_latent_pair_stats's (P, 3)),
+                        ca = sin((1 - t) omega) / sin(omega), cb = sin(t omega) / sin(omega): the endpoints are not normalised, the
+                        usual latent slerp; the lerp coefficients where sum a^2 == 0, sum b^2 == 0, sin(omega) < VCG_SLERP_MIN_SIN
+                        or a stat is not finite.
+   j == 0 writes a[p] and j == T - 1 writes b[p], bit for bit (a NaN keeps its payload, -0 its sign).  Elsewhere, in fp32,
+     z = fmaf(ca, a, __fmul_rn(cb, b)):
+   an explicit fused multiply-add over an explicit product, two roundings, no compiler-chosen contraction.  A value depends on
+   (pair, j, T, mode) only, never on first or k: a path computed in one call or in chunks has the same bits.  Pad lanes of z are 0.
+   coef_out, if not NULL: (P, k, 2) fp32, the (ca, cb) used ((1, 0) and (0, 1) at the two ends).  stats is not read by the lerp and
+   may then be NULL.  z must not overlap a or b.
+   16-byte loads and stores; a lane loads its float4 of a and of b once and keeps them in registers over the k fractions, whose
+   coefficients the workgroup staged in LDS: (2 + k) per floats of traffic per pair.  Grid (blocks over per, pairs), grid-stride.
+   Refused (non-zero, vcg_last_error, nothing launched): an unknown mode; a, b or z null, stats null with the slerp; P < 1;
+   per == 0 or > 2^31; pitch % 4 != 0, C < 1, C > pitch or per % pitch != 0; T < 2; k < 1, first < 0 or first + k > T; a, b or z
+   not 16-byte aligned, stats or coef_out not 8-byte aligned. */
+int vcg_latent_path(const float* a, const float* b, const double* stats, float* z, float* coef_out, int P, int T, int first, int k,
+                    size_t per, int C, int pitch, int mode, void* stream);
+
 /* Sliced Wasserstein distance on Laplacian-pyramid patches (new: the reference compares unpaired runs by eye only; Karras et
    al., ICLR 2018, section 5) — csrc/swd.hip.  Forward only.  No float atomics: every call gives the same bits for the same input.
    The stages of one pyramid level, in order: vcg_swd_pyramid_level, vcg_swd_gather, vcg_swd_normalize, vcg_swd_project,

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # VCG_LIBVCG: load another build of the same sources (A/B runs of kernel variants, tools/); the default is the in-tree library
 LIB_PATH = os.environ.get("VCG_LIBVCG") or os.path.join(_HERE, "libvcg.so")
-SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip", "swd_loss.hip", "msssim_loss.hip", "kl_free_bits.hip", "patch_head.hip", "gan_terms.hip", "feature_match.hip"]
+SOURCES = ["conv_igemm.hip", "conv_thin.hip", "conv_thinin.hip", "conv_wino.hip", "conv_slab.hip", "conv_ring.hip", "gemm_split.hip", "norm.hip", "misc.hip", "input.hip", "metrics.hip", "image_io.hip", "ssim_loss.hip", "grad_loss.hip", "freq_loss.hip", "grad_clip.hip", "ema.hip", "image_pool.hip", "sample_stats.hip", "swd.hip", "swd_loss.hip", "msssim_loss.hip", "kl_free_bits.hip", "patch_head.hip", "gan_terms.hip", "feature_match.hip", "latent_path.hip"]
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vcg.h")
 
 _c = ctypes
@@ -131,6 +131,9 @@ SIGNATURES = {
     "vcg_sample_accumulate": (_I, [_P, _P, _P, _I, _I, _I, _Z, _P]),
     "vcg_spread_workspace": (_Z, [_I, _I, _I]),
     "vcg_spread_display_hw": (_I, [_P, _I, _F, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "vcg_latent_stats_workspace": (_Z, [_I, _Z]),
+    "vcg_latent_pair_stats": (_I, [_P, _P, _P, _I, _Z, _I, _I, _P, _Z, _P]),
+    "vcg_latent_path": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _Z, _I, _I, _I, _P]),
     "vcg_swd_pyramid_level": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "vcg_swd_gather": (_I, [_P, _I, _I, _I32P, _I, _P, _Z, _Z, _P]),
     "vcg_swd_normalize_workspace": (_Z, [_I]),

@@ -2157,6 +2157,65 @@ def spread_display_hw(m2, count, window=None, gain=2.0, uint8=False):
     return ((f32, u8) if uint8 == "both" else u8 if uint8 else f32), res
 
 
+# ------------------------------------------------------------------ the interpolating translator (translate.py --interpolate N)
+LATENT_PATH_MODES = ("slerp", "lerp")                # the index is the library's VCG_LATENT_* code
+
+
+def _pair_phys_maps(a, b, what):
+    _require_gpu(a, what)
+    _require_gpu(b, what)
+    if a.dim() != 4 or a.shape != b.shape or a.shape[0] < 1:
+        raise RuntimeError(f"{what}: a and b must be two (P, C, h, w) maps of one shape with P >= 1, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return as_phys(a), as_phys(b)                    # two views of one encoder batch (mu[:-1], mu[1:]) alias it: nothing is copied
+
+
+def latent_pair_stats(a, b):
+    """[sum a[p]^2, sum b[p]^2, sum a[p] b[p]] of each pair of logical (P, C, h, w) latent maps, over the logical channels, summed
+    in double in a fixed order -> a device (P, 3) float64 tensor (csrc/latent_path.hip).  Inference only."""
+    ap, bp = _pair_phys_maps(a, b, "latent_pair_stats")
+    n, c, h, w = a.shape
+    per = h * w * pitch(c)
+    lib = _native.lib()
+    ws = torch.empty(max(lib.vcg_latent_stats_workspace(n, per), 8) // 8, dtype=torch.float64, device=a.device)
+    out = torch.empty((n, 3), dtype=torch.float64, device=a.device)
+    _native.check(lib.vcg_latent_pair_stats(_ptr(ap), _ptr(bp), _ptr(out), n, per, c, pitch(c), _ptr(ws), ws.numel() * 8, _stream()),
+                  "vcg_latent_pair_stats")
+    return out
+
+
+def latent_path(a, b, steps, mode="slerp", first=0, count=None, stats=None, return_coef=False):
+    """Inference only (no autograd node): the fractions first .. first + count - 1 of the T = steps + 2 uniform fractions
+    t_j = j / (T - 1) of the path from a[p] to b[p], logical (P, C, h, w) maps -> a logical (P * count, C, h, w) batch with fraction
+    j of pair p at index p * count + (j - first): what a decoder takes.  `steps` counts the INTERMEDIATE frames; j == 0 is a[p] and
+    j == T - 1 is b[p], bit for bit.  mode "slerp": z = (sin((1 - t) w) a + sin(t w) b) / sin(w) with w the angle between the two
+    maps, the straight line where they are (anti)parallel or empty (VCG_SLERP_MIN_SIN); "lerp": z = (1 - t) a + t b.  A value does
+    not depend on the chunking (first, count).  stats: `latent_pair_stats(a, b)` if the caller has it (the slerp computes it
+    otherwise; the lerp does not use it).  return_coef: also the (P, count, 2) fp32 coefficients (ca, cb) that were used."""
+    if mode not in LATENT_PATH_MODES:
+        raise ValueError(f"latent_path: mode must be one of {LATENT_PATH_MODES}, got {mode!r}")
+    ap, bp = _pair_phys_maps(a, b, "latent_path")
+    n, c, h, w = a.shape
+    total = int(steps) + 2
+    first = int(first)
+    count = total - first if count is None else int(count)
+    if total < 2 or count < 1 or first < 0 or first + count > total:
+        raise RuntimeError(f"latent_path: steps={steps}, first={first}, count={count}: the path has the {max(total, 0)} fractions "
+                           f"0 .. steps + 1 and a call takes at least one of them")
+    if mode == "slerp":
+        if stats is None:
+            stats = latent_pair_stats(a, b)
+        elif not stats.is_cuda or stats.dtype != torch.float64 or tuple(stats.shape) != (n, 3) or not stats.is_contiguous():
+            raise RuntimeError(f"latent_path: stats must be latent_pair_stats's (P, 3) float64 device tensor, got {stats.dtype} "
+                               f"{tuple(stats.shape)} on {stats.device}")
+    else:
+        stats = None
+    z = torch.empty((n * count, h, w, pitch(c)), dtype=torch.float32, device=a.device)
+    coef = torch.empty((n, count, 2), dtype=torch.float32, device=a.device) if return_coef else None
+    _native.check(_native.lib().vcg_latent_path(_ptr(ap), _ptr(bp), _ptr(stats), _ptr(z), _ptr(coef), n, total, first, count,
+                                                h * w * pitch(c), c, pitch(c), LATENT_PATH_MODES.index(mode), _stream()), "vcg_latent_path")
+    return (logical_of(z, c), coef) if return_coef else logical_of(z, c)
+
+
 # ------------------------------------------------------------------ sliced Wasserstein distance (swd.py, csrc/swd.hip)
 SWD_MAX_DESC = 16384              # descriptors per set and level: a sorted column lives in 64 KiB of LDS (VCG_SWD_MAX_DESC)
 SWD_PATCH = 7

@@ -16,6 +16,10 @@ test.py shows for them, which is the reconstruction decoder_A(encoder(x)) their 
 `--samples K` (variational generators): K draws per frame from ONE encoder pass — the latent's mu and logvar do not depend on eps —
 decoded in chunks of as many samples as the pixel bound admits, with the running mean and the per-pixel spread of the draws
 accumulated on the device (csrc/sample_stats.hip; DESIGN.md, "Sampling translator").
+
+`--interpolate N` (variational generators): N frames between each two consecutive inputs, decoded from a path through latent
+space between the two frames' latent means — every frame encoded once, the path (spherical by default) computed on the device
+(csrc/latent_path.hip; DESIGN.md, "Interpolating translator").
 """
 import argparse
 import json
@@ -257,6 +261,165 @@ def sample_images(model, architecture, frames, samples, direction="a2b", seed=12
     return sample_padded(model, architecture, x, window, samples, direction, temperature, eps, chunk, spread_gain, debug=debug)
 
 
+# ------------------------------------------------------------------ N frames between two inputs
+def _check_interpolation(steps, mode):
+    if steps < 1:
+        raise ValueError(f"interpolate: at least 1 intermediate frame, got {steps}")
+    if mode not in ops.LATENT_PATH_MODES:
+        raise ValueError(f"interp_mode must be one of {', '.join(ops.LATENT_PATH_MODES)}, got {mode!r}")
+
+
+def interpolate_padded(model, architecture, x, window, steps, direction="a2b", mode="slerp", chunk=None, debug=False, carry=None):
+    """`interpolate_images` on a loaded logical (N, 3, Hp, Wp) batch whose frames are `window` of it.  `carry`: the latent mean
+    of the frame BEFORE x[0] (a previous call's "last_mu"), which then opens the first pair: N pairs instead of N - 1, and no
+    frame is encoded twice.  The result also holds "last_mu", the (1, C, h, w) latent mean of x[-1].  One frame without a carry
+    gives no pair: empty tensors and its "last_mu" (how a folder starts at --batch_size 1)."""
+    latent, decode = sampler_of(model, architecture, direction)
+    _check_interpolation(steps, mode)
+    n, _, hp, wp = x.shape
+    top, left, h, w = window
+    pairs = n - 1 if carry is None else n
+    total = steps + 2
+    plan = sample_chunks(pairs, hp, wp, total, chunk) if pairs >= 1 else []
+    model.eval()
+    with torch.no_grad():
+        mu, _ = latent(x)                                           # the one encoder pass; the path runs on the means: no eps draw
+        c = mu.shape[1]
+        if carry is not None:
+            if tuple(carry.shape) != (1,) + tuple(mu.shape[1:]):
+                raise RuntimeError(f"carry has shape {tuple(carry.shape)}, expected {(1,) + tuple(mu.shape[1:])}")
+            mu = ops.logical_of(torch.cat([ops.as_phys(carry), ops.as_phys(mu)]), c)
+        out = {"last_mu": ops.logical_of(ops.as_phys(mu[-1:]).clone(), c)}
+        frames = torch.empty((pairs, total, h, w, 3), dtype=torch.float32 if debug else torch.uint8, device=x.device)
+        step = torch.empty((pairs, total - 1), dtype=torch.float32, device=x.device)
+        stats = torch.empty((pairs, 3), dtype=torch.float64, device=x.device)
+        coefs, latents, prev = [], [], None
+        if pairs >= 1:
+            a, b = mu[:-1], mu[1:]                                  # consecutive frames: two views of the one batch
+            stats = ops.latent_pair_stats(a, b)
+        for first, k in plan:
+            z = ops.latent_path(a, b, steps, mode, first, k, stats=stats, return_coef=debug)
+            if debug:
+                z, coef = z
+                coefs.append(coef)
+                latents.append(z.reshape(pairs, k, *z.shape[1:]))
+            y = decode(z)                                           # (P * k, 3, Hp, Wp), fraction j of pair p at p * k + (j - first)
+            shown = ops.to_display_hw(y, window).view(pairs, k, h, w, 3)
+            frames[:, first:first + k] = shown if debug else ops.to_display_hw(y, window, uint8=True).view(pairs, k, h, w, 3)
+            # the steps between consecutive frames as the viewer sees them: the clamped frames back at pitch 4, the previous
+            # chunk's last frame in front, and ONE metrics launch over the run shifted by one frame (the step from a pair's last
+            # frame to the next pair's first is computed with the rest and dropped)
+            lead = 0 if prev is None else 1
+            run = torch.zeros((pairs, lead + k, h, w, 4), dtype=torch.float32, device=x.device)
+            run[:, lead:, :, :, :3] = shown
+            if lead:
+                run[:, 0] = prev
+            prev = run[:, -1].clone()
+            if lead + k >= 2:
+                flat = ops.logical_of(run.view(pairs * (lead + k), h, w, 4), 3)
+                l1 = ops.image_metrics_hw(flat[1:], flat[:-1])[:, 0]
+                step[:, first - lead:first + k - 1] = torch.cat([l1, l1.new_zeros(1)]).view(pairs, lead + k)[:, :lead + k - 1]
+        cos = (stats[:, 2] / (stats[:, 0] * stats[:, 1]).sqrt()).clamp(-1.0, 1.0)
+        out.update(frames=frames, step_l1=step, omega=torch.acos(cos).float(), norm_a=stats[:, 0].sqrt().float(),
+                   norm_b=stats[:, 1].sqrt().float())
+        if debug and plan:
+            out.update(coef=torch.cat(coefs, dim=1), latents=torch.cat(latents, dim=1))
+    return out
+
+
+def interpolate_images(model, architecture, frames, steps, direction="a2b", mode="slerp", chunk=None, device=None, debug=False):
+    """`steps` >= 1 frames between each two consecutive uint8 frames (as translate_images takes them; at least two) by a
+    variational generator: every frame is encoded once, pair p is (frame p, frame p + 1), and the T = steps + 2 latents
+    z(t_j), t_j = j / (T - 1), of each pair's path between the two latent MEANS are decoded -> a dict of device tensors:
+      frames   uint8 (P, T, H, W, 3); frames[p, 0] is the translation of frame p at its latent mean, frames[p, T - 1] that of
+               frame p + 1;
+      omega    fp32 (P,), the angle between the two latent means (NaN where one is all zeros); norm_a, norm_b their 2-norms;
+      step_l1  fp32 (P, T - 1), the mean absolute difference between consecutive decoded frames as displayed.
+    mode "slerp" walks the great circle (ops.latent_path), "lerp" the straight line.  The path is deterministic: no eps is drawn and
+    the ops stream does not move.  The decoder runs on chunks of fractions (`sample_chunks`; `chunk` lowers the chunk size); a
+    latent does not depend on the chunking.  debug: frames as fp32 clamped to [0, 1], "coef" (P, T, 2), the path coefficients
+    that were used, and "latents" (P, T, C, h, w)."""
+    frames = _as_frames(frames)
+    n, h, w, _ = frames.shape
+    sampler_of(model, architecture, direction)                      # refusals come before anything is copied
+    _check_interpolation(steps, mode)
+    if n < 2:
+        raise ValueError(f"interpolate: a path needs two frames, got {n}")
+    ops.check_translate_size(n, h, w)
+    device = device or next(model.parameters()).device
+    x, window = ops.image_load(frames.to(device, non_blocking=True))
+    return interpolate_padded(model, architecture, x, window, steps, direction, mode, chunk, debug)
+
+
+def unevenness(step_l1):
+    """max / mean of a pair's steps: 1 for a path whose decoded frames move evenly, large where it jumps; None when the mean is 0
+    (nothing moved) or a step is not finite."""
+    steps = [float(v) for v in step_l1]
+    if not steps or not all(math.isfinite(v) for v in steps):
+        return None
+    mean = sum(steps) / len(steps)
+    return max(steps) / mean if mean > 0 else None
+
+
+def interpolation_output_names(paths, steps):
+    """[(file name, input index i, fraction j)] in path order: <stem(i)>_i00.png is input i itself (fraction 0 of the pair it
+    opens; the last input: the end of the pair it closes), <stem(i)>_i01.png ... the `steps` frames between it and the next
+    input.  A sorted listing of the names of sorted stems is the path: len(paths) + (len(paths) - 1) * steps pictures."""
+    width = max(2, len(str(steps)))
+    last = len(paths) - 1
+    return [(f"{Path(p).stem}_i{j:0{width}d}.png", i, j) for i, p in enumerate(paths) for j in range(1 if i == last else steps + 1)]
+
+
+def interpolation_windows(n, batch_size):
+    """[(start, stop, pairs)]: the encoder batches frames[start:stop] of a folder of n frames, at most `batch_size` each, and the
+    pairs (i, i + 1) each decodes.  Every window but the first is handed the latent of the frame before it, so every frame is
+    in exactly one batch and every consecutive pair in exactly one window."""
+    if n < 1 or batch_size < 1:
+        raise ValueError(f"interpolation_windows: n={n}, batch_size={batch_size}")
+    return [(s, min(s + batch_size, n), [(i, i + 1) for i in range(max(s - 1, 0), min(s + batch_size, n) - 1)])
+            for s in range(0, n, batch_size)]
+
+
+def interpolation_record(name_a, name_b, omega, norm_a, norm_b, step_l1):
+    """One pair's entry of metrics.json."""
+    return {"a": name_a, "b": name_b, "omega": _finite_or_none(float(omega)), "norm_a": _finite_or_none(float(norm_a)),
+            "norm_b": _finite_or_none(float(norm_b)), "step_l1": [_finite_or_none(float(v)) for v in step_l1],
+            "unevenness": unevenness(step_l1)}
+
+
+def check_interpolation_args(args):
+    """The refusals of --interpolate that need nothing but the command line."""
+    if args.interpolate < 1:
+        raise ValueError(f"--interpolate must be at least 1 (intermediate frames between two inputs), got {args.interpolate}")
+    if args.samples > 1:
+        raise ValueError("--interpolate walks between the latent means of two frames: it cannot be combined with --samples (draws around one frame)")
+    if args.targets:
+        raise ValueError("--interpolate cannot be combined with --targets: the frames between two inputs have no expected image")
+
+
+def check_interpolation_inputs(paths, shapes, batch_size, steps):
+    """The refusals of --interpolate that need the list of inputs and their sizes ((H, W, C) each), before a model is loaded."""
+    if len(paths) < 2:
+        raise ValueError(f"--interpolate needs at least two inputs to walk between, found {len(paths)}")
+    for p, s in zip(paths[1:], shapes[1:]):
+        if tuple(s[:2]) != tuple(shapes[0][:2]):
+            raise ValueError(f"--interpolate: all frames of a run must have one size, but {Path(paths[0]).name} is {shapes[0][0]}x{shapes[0][1]} "
+                             f"and {Path(p).name} is {s[0]}x{s[1]}; use --size S to resize every frame to S x S")
+        if tuple(s) != tuple(shapes[0]):
+            raise ValueError(f"--interpolate: {Path(paths[0]).name} decodes to {shapes[0][2]} channel(s) and {Path(p).name} to {s[2]}; "
+                             f"convert them to one mode")
+    h, w = shapes[0][:2]
+    if h < ops.MIN_TRANSLATE_SIDE or w < ops.MIN_TRANSLATE_SIDE:
+        raise ValueError(f"--interpolate: the {h}x{w} frames are smaller than {ops.MIN_TRANSLATE_SIDE} on a side")
+    hp, wp, _, _ = ops.pad_plan(h, w)
+    try:
+        sample_chunks(min(batch_size, len(paths)), hp, wp, steps + 2)
+    except ValueError:
+        raise ValueError(f"--interpolate {steps}: the {steps + 2} frames of a pair are decoded in chunks of whole windows, and one window of "
+                         f"{min(batch_size, len(paths))} x {hp}x{wp} padded pixels exceeds the bound of {ops.MAX_TRANSLATE_PIXELS} per "
+                         f"batch: use a smaller --batch_size or --size") from None
+
+
 # ------------------------------------------------------------------ files
 def discover_inputs(path):
     """The image files of `path` (one file, or the files of a directory in name order)."""
@@ -353,6 +516,12 @@ def build_parser():
                    help="with --samples: the spread PNG shows min(1, G * s).  The sample standard deviation s of K values in [0, 1] "
                         "cannot exceed 0.5 sqrt(K / (K - 1)), so the default 2 saturates only near that theoretical maximum: it is "
                         "derived, not tuned on a model, and a real model's maps are far darker — you will usually raise it")
+    p.add_argument("--interpolate", type=int, default=None, metavar="N",
+                   help="variational generators: write N frames between each two consecutive inputs (in name order), decoded from a "
+                        "path between the two frames' latent means: <stem>_i00.png is the input's own translation, <stem>_i01.png ... "
+                        "the frames towards the next input.  All frames must have one size (or use --size)")
+    p.add_argument("--interp_mode", choices=list(ops.LATENT_PATH_MODES), default="slerp",
+                   help="with --interpolate: slerp walks the great circle between the two latents, lerp the straight line")
     p.add_argument("--batch_size", type=int, default=1, help="frames of equal size are translated together, at most this many")
     p.add_argument("--size", type=int, default=None,
                    help="first resize every frame to SIZE x SIZE (the reference's Resize((S, S)); a multiple of 16, at least 32)")
@@ -485,6 +654,69 @@ def _device():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def run_interpolation(args):
+    """--interpolate N: the whole run.  Everything that can be refused is refused before the model is loaded."""
+    check_interpolation_args(args)
+    arch = checkpoint_architecture(args.checkpoint, args.architecture)
+    if arch not in VARIATIONAL:
+        raise ValueError(f"--interpolate needs a variational checkpoint ({', '.join(VARIATIONAL)}); {arch} has no latent distribution to walk")
+    paths = discover_inputs(args.input)
+    if args.size is not None:
+        shapes = [(args.size, args.size, 3)] * len(paths)
+    else:
+        shapes = [probe(p) for p in paths] if len(paths) >= 2 else []
+    check_interpolation_inputs(paths, shapes, args.batch_size, args.interpolate)
+    device = _device()
+    model, architecture = load_generator(args.checkpoint, args.architecture, args.latent_dim, None, device, ema=args.ema)
+    generator_of(model, architecture, args.direction)
+    print("--interpolate: the path runs between the latent means, so --eps is not used and no noise is drawn")
+    out_dir = Path(args.output)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    steps, last = args.interpolate, len(paths) - 1
+    name_of = {(i, j): name for name, i, j in interpolation_output_names(paths, steps)}
+    records = []
+    pool = ThreadPoolExecutor(max_workers=max(1, args.num_workers))
+
+    def write(pair_list, res):
+        from PIL import Image
+        u8 = res["frames"].cpu().numpy()
+        omega, norm_a, norm_b, step_l1 = (res[k].cpu().double().numpy() for k in ("omega", "norm_a", "norm_b", "step_l1"))
+        jobs = []
+        for idx, (i, nxt) in enumerate(pair_list):
+            jobs += [(name_of[(i, j)], u8[idx, j]) for j in range(steps + 1)]
+            if nxt == last:
+                jobs.append((name_of[(last, 0)], u8[idx, steps + 1]))
+            records.append(interpolation_record(paths[i].name, paths[nxt].name, omega[idx], norm_a[idx], norm_b[idx], step_l1[idx]))
+            print(f"  {paths[i].name} -> {paths[nxt].name}: {name_of[(i, 0)]} .. {name_of[(i, steps)]}")
+        list(pool.map(lambda job: Image.fromarray(job[1]).save(out_dir / job[0]), jobs))
+
+    carry = None
+    if args.size is not None:
+        pipe = input_pipeline.DeviceInputPipeline(_PairFiles(paths, None), args.batch_size, args.size, device, recipe="test",
+                                                  shuffle=False, seed=args.seed, num_workers=max(1, args.num_workers), same_xy=True)
+        done = 0
+        for batch in pipe:
+            x = ops.to_nhwc(batch["x"])
+            n, _, hp, wp = x.shape
+            res = interpolate_padded(model, architecture, x, (0, 0, hp, wp), steps, args.direction, args.interp_mode, carry=carry)
+            write([(i, i + 1) for i in range(max(done - 1, 0), done + n - 1)], res)
+            carry, done = res["last_mu"], done + n
+    else:
+        for start, stop, pair_list in interpolation_windows(len(paths), args.batch_size):
+            frames = load_batch(paths[start:stop], shapes[0], pool)
+            x, window = ops.image_load(frames.to(device, non_blocking=True))
+            res = interpolate_padded(model, architecture, x, window, steps, args.direction, args.interp_mode, carry=carry)
+            write(pair_list, res)
+            carry = res["last_mu"]
+    pool.shutdown()
+    report = out_dir / "metrics.json"
+    with open(report, "w") as f:
+        json.dump({"interpolation": {"mode": args.interp_mode, "steps": steps, "pairs": records}}, f, indent=2, allow_nan=False)
+    print(f"Saved metrics to: {report}")
+    print(f"Wrote {len(name_of)} frame(s) of {len(paths)} input(s) into {out_dir}")
+    return 0
+
+
 def main(argv=None):
     """Returns the exit code: 0, or 1 when some frame was skipped (too small, too large, unreadable, no target)."""
     args = build_parser().parse_args(argv)
@@ -492,6 +724,8 @@ def main(argv=None):
         raise ValueError("--batch_size must be at least 1")
     if args.size is not None and (args.size < ops.MIN_TRANSLATE_SIDE or args.size % 16):
         raise ValueError(f"--size must be a multiple of 16 and at least {ops.MIN_TRANSLATE_SIDE}")
+    if args.interpolate is not None:
+        return run_interpolation(args)
     if args.samples < 1:
         raise ValueError("--samples must be at least 1")
     if args.samples >= 2:
